@@ -1,9 +1,27 @@
 """bench.py -- DDPG gradient steps / second of the fused MI355X path (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 200 --warmup 50
+    python bench.py --gpus 1 --steps 200 --warmup 50 --full    # + every other figure and check listed below
+    python bench.py --gpus 1 --steps 200 --warmup 50 --dump-outputs DIR
     python bench.py --gpus N --steps K --warmup W          # N > 1: launches the N ranks itself (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, takes W warm-up steps, times K steps and prints the result line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, `losses` of the last step).  Everything else on
+the line -- the probe steps and in-kernel stamps behind `roofline` / `kernels`, the synchronous-loop and host-fed rates, both
+arithmetic modes, `sa_kernel_hbm` / `sa_kernel_mfma`, `cpu_baseline`, the replica check of N > 1 -- is measured with `--full` only
+(`--no-cpu-baseline`, `--no-host-rate`, `--no-sa-kernel` and `--probe-steps` trim a --full run).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy -- the loss dict
+update_parameters returns (float64 scalars) and the step's policy / critic / TD-target tensors the agent keeps (float32; a
+fixed, seeded sample of any array above 2 M values).  The inputs depend on the
+arguments alone (seeded weights, replay buffer, minibatches and TD3 noise), so two builds compare output for output.  A step is
+not bit-reproducible (f64 atomics in varying order, DESIGN.md section 8: one step repeats to rounding) and training amplifies
+that from step to step (after 250 steps two runs differed in pi by up to 0.7).  So with --dump-outputs the last timed step starts
+from the seeded initial state again -- parameters of every network and their Adam moments, restored between fences before it is
+enqueued -- and takes its own minibatch, noise draw and step index: what it returns repeats from run to run to rounding.  The
+agent's internal state is not dumped: the backward's atomic sums leave the actor phase's encoder gradients a few 1e-4 apart
+(entry-relative) between runs, and Adam turns an entry whose gradient is zero up to rounding into a step of about +-lr.
 
 Workload (BASELINE.json configs[1], SURVEY 8d "config 2"): DDPG/TD3 update with goal-auxiliary heads
 (ddpg_td3_aux.yaml), batch 256 per GPU, 1024-point clouds, synthetic seeded replay buffer, random-init
@@ -181,7 +199,48 @@ def parse():
                                                                 "(roofline / kernel table), after the timed region")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-rate", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="every figure and check beyond the headline rate (roofline, kernel "
+                                                        "table, sync / host-fed rates, both modes, SA kernels, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_CAP = 2 * 1024 * 1024       # values per dumped array; larger arrays are sampled at fixed, seeded positions
+STATE_FLATS = ("pol", "pol_t", "cr", "cr_t", "enc", "venc")      # every network the update step reads and writes
+
+
+def training_state(rt):
+    """copies of what a step carries over to the next one: the parameters of every network (targets included) and their Adam
+    moments (the optimiser's step counts, learning-rate schedules and the minibatch ring follow from the step index alone)"""
+    return {n: [t.clone() for t in (f.master, f.exp_avg, f.exp_avg_sq)] for n in STATE_FLATS for f in [getattr(rt, n).flat]}
+
+
+def restore_training_state(rt, state):
+    for n, saved in state.items():
+        f = getattr(rt, n).flat
+        for dst, src in zip((f.master, f.exp_avg, f.exp_avg_sq), saved):
+            dst.copy_(src)
+        f.sync_packed()                                      # the packed layout and the split-bf16 mirrors follow `master`
+
+
+def dump_outputs(out_dir, result, tensors):
+    """`result`: the loss dict of the last timed step; `tensors`: name -> host copy of what that step left on the agent"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss_" + k: np.asarray([float(v)], dtype=np.float64) for k, v in result.items()}
+    for name, t in tensors.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_CAP:
+            pick = np.sort(np.random.default_rng(SEED).choice(a.size, DUMP_CAP, replace=False))
+            a = a.reshape(-1)[pick]
+        arrays[name] = np.ascontiguousarray(a, dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 * 1024 * 1024, "dump of %d bytes exceeds 64 MB" % total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def cpu_baseline(cfg, batch, noise):
@@ -363,6 +422,8 @@ def main():
         agent._dp = dp
         dp.attach(rt)
         dp.broadcast_parameters([rt.pol.flat, rt.pol_t.flat, rt.cr.flat, rt.cr_t.flat, rt.enc.flat, rt.venc.flat])
+    # --dump-outputs: the seeded initial state, which the last timed step starts from again (see the module docstring)
+    initial_state = training_state(rt) if args.dump_outputs else None
     from ga_ddpg_amd.runtime import BATCH_KEYS
     ring = []
     for hb in host_batches:
@@ -390,63 +451,78 @@ def main():
     for i in range(args.warmup):
         step(i)
 
-    # ---- which kernel dominates?  in-kernel wall-clock stamps of every tagged launch during a few extra warm-up
-    # steps, inside the overlapped step -- and once more with the step serialised on one stream (the kernel by itself)
-    def probe(serial, n):
-        engine.SERIAL = serial
-        engine.timing_start("*", capacity=n * 200)
-        for i in range(n):
-            step(args.warmup + i)
-        acc = engine.timing_stop()
-        ROUTES.update(engine.timing_routes())
-        engine.SERIAL = False
-        return acc
-    probe_n = args.probe_steps + args.probe_steps % 2            # policy and non-policy steps in equal number
-    by_tag = probe(False, probe_n)
-    alone = probe(True, probe_n) if world == 1 else {}
-    rows = {"sa1": int(rt.geo.rows[0]["n"].item()), "sa2": int(rt.geo.rows[1]["n"].item()),
-            "sa3": int(rt.geo.rows[2]["n"].item()), "fc": B}
-    table = kernel_table(by_tag, rows, B, probe_n)
-    table_alone = kernel_table(alone, rows, B, probe_n) if alone else {}
-    priced = {k: v for k, v in table.items() if v["bound"] in ("mfma", "hbm")}
-    dom = max(priced, key=lambda k: priced[k]["ms_per_step"])
-    # two symbols run neck and neck (the wide forward on the chains, 27 launches; the wide dW on its side lanes, 12 launches whose
-    # in-step duration is inflated 2-3 x by what runs beside them) and the probe's order flipped from run to run: among the
-    # symbols within 5 % of the largest in-step time, the one with the most STAND-ALONE time per step is the dominant kernel
-    near = [k for k in priced if priced[k]["ms_per_step"] >= 0.95 * priced[dom]["ms_per_step"]]
-    if len(near) > 1 and table_alone:
-        dom = max(near, key=lambda k: table_alone.get(k, {}).get("ms_per_step", 0.0))
-    # ---- the timed region: K steps, HIP events around the launches of the dominant kernel only
-    engine.timing_start(frozenset(table[dom]["tags"]), capacity=min(8192, int((args.steps // 4 + 1) * table[dom]["launches_per_step"] * 1.1) + 64))
+    if args.full:
+        # ---- which kernel dominates?  in-kernel wall-clock stamps of every tagged launch during a few extra warm-up
+        # steps, inside the overlapped step -- and once more with the step serialised on one stream (the kernel by itself)
+        def probe(serial, n):
+            engine.SERIAL = serial
+            engine.timing_start("*", capacity=n * 200)
+            for i in range(n):
+                step(args.warmup + i)
+            acc = engine.timing_stop()
+            ROUTES.update(engine.timing_routes())
+            engine.SERIAL = False
+            return acc
+        probe_n = args.probe_steps + args.probe_steps % 2            # policy and non-policy steps in equal number
+        by_tag = probe(False, probe_n)
+        alone = probe(True, probe_n) if world == 1 else {}
+        rows = {"sa1": int(rt.geo.rows[0]["n"].item()), "sa2": int(rt.geo.rows[1]["n"].item()),
+                "sa3": int(rt.geo.rows[2]["n"].item()), "fc": B}
+        table = kernel_table(by_tag, rows, B, probe_n)
+        table_alone = kernel_table(alone, rows, B, probe_n) if alone else {}
+        priced = {k: v for k, v in table.items() if v["bound"] in ("mfma", "hbm")}
+        dom = max(priced, key=lambda k: priced[k]["ms_per_step"])
+        # two symbols run neck and neck (the wide forward on the chains, 27 launches; the wide dW on its side lanes, 12 launches whose
+        # in-step duration is inflated 2-3 x by what runs beside them) and the probe's order flipped from run to run: among the
+        # symbols within 5 % of the largest in-step time, the one with the most STAND-ALONE time per step is the dominant kernel
+        near = [k for k in priced if priced[k]["ms_per_step"] >= 0.95 * priced[dom]["ms_per_step"]]
+        if len(near) > 1 and table_alone:
+            dom = max(near, key=lambda k: table_alone.get(k, {}).get("ms_per_step", 0.0))
+        # HIP events around the launches of the dominant kernel only, in the timed region below
+        engine.timing_start(frozenset(table[dom]["tags"]), capacity=min(8192, int((args.steps // 4 + 1) * table[dom]["launches_per_step"] * 1.1) + 64))
+    # ---- the timed region: K steps
     fence()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        # the stamps cost the timed kernels ~3 % (two s_memrealtime + stores per wavefront): taken on a quarter of the steps
-        engine.TIMING["enabled"] = (i % 8 in (0, 3))        # steps with and without the actor-critic term alike
+        if args.full:
+            # the stamps cost the timed kernels ~3 % (two s_memrealtime + stores per wavefront): taken on a quarter of the steps
+            engine.TIMING["enabled"] = (i % 8 in (0, 3))        # steps with and without the actor-critic term alike
+        if initial_state is not None and i == args.steps - 1:
+            # every earlier step is complete before the state is replaced, and the copies before the last step is enqueued
+            agent.flush()
+            fence()
+            restore_training_state(rt, initial_state)
+            fence()
         out = step(args.warmup + i)
     fence()
     dt = time.perf_counter() - t0
-    timed_tags = engine.timing_stop()
-    # the same steps with the host waiting for each result before it enqueues the next (the reference's loop reads its
-    # losses with .item() every step): uploads, geometry and ~2 ms of launch calls then sit in front of every step
-    n_sync = max(10, args.steps // 5)
-    fence()
-    t1 = time.perf_counter()
-    for i in range(n_sync):
-        step(args.warmup + args.steps + i, sync=True)
-    fence()
-    rate_sync = n_sync / (time.perf_counter() - t1)
-    # ... and the same synchronous loop with the NEXT minibatch handed to agent.prefetch() before each update (what
-    # core.train_test_offline.train_off_policy does by default: it samples one minibatch ahead): upload + geometry of step N + 1
-    # run beside step N, the loop still reads every step's losses before it enqueues the next
-    fence()
-    t1 = time.perf_counter()
-    base = args.warmup + args.steps + n_sync
-    for i in range(n_sync):
-        agent.prefetch(ring[(base + i + 1) % len(ring)])
-        step(base + i, sync=True)
-    fence()
-    rate_sync_prefetch = n_sync / (time.perf_counter() - t1)
+    if args.dump_outputs and rank == 0:
+        # read before anything else runs on the agent: these are the buffers of the last timed step
+        tensors = {"pi": agent.pi, "aux_pred": agent.aux_pred, "qf1": agent.qf1, "qf2": agent.qf2,
+                   "next_q_value": agent.next_q_value, "critic_grasp_aux": agent.critic_grasp_aux}
+        dump_outputs(args.dump_outputs, dict(out.items()), tensors)
+    if args.full:
+        timed_tags = engine.timing_stop()
+        # the same steps with the host waiting for each result before it enqueues the next (the reference's loop reads its
+        # losses with .item() every step): uploads, geometry and ~2 ms of launch calls then sit in front of every step
+        n_sync = max(10, args.steps // 5)
+        fence()
+        t1 = time.perf_counter()
+        for i in range(n_sync):
+            step(args.warmup + args.steps + i, sync=True)
+        fence()
+        rate_sync = n_sync / (time.perf_counter() - t1)
+        # ... and the same synchronous loop with the NEXT minibatch handed to agent.prefetch() before each update (what
+        # core.train_test_offline.train_off_policy does by default: it samples one minibatch ahead): upload + geometry of step N + 1
+        # run beside step N, the loop still reads every step's losses before it enqueues the next
+        fence()
+        t1 = time.perf_counter()
+        base = args.warmup + args.steps + n_sync
+        for i in range(n_sync):
+            agent.prefetch(ring[(base + i + 1) % len(ring)])
+            step(base + i, sync=True)
+        fence()
+        rate_sync_prefetch = n_sync / (time.perf_counter() - t1)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -458,7 +534,8 @@ def main():
         # of this run (all-reduced MAX / MIN of an int64 checksum) -- a collective, so every rank takes part
         torch.cuda.synchronize()
         dp_info = dp.transport()
-        dp_info["replicas_bit_identical"] = dp.replicas_agree([rt.pol.flat, rt.pol_t.flat, rt.cr.flat, rt.cr_t.flat, rt.enc.flat, rt.venc.flat])
+        if args.full:
+            dp_info["replicas_bit_identical"] = dp.replicas_agree([rt.pol.flat, rt.pol_t.flat, rt.cr.flat, rt.cr_t.flat, rt.enc.flat, rt.venc.flat])
         dp_info["bucketed_exchange"] = bool(getattr(rt, "bucketed", False))
         dp.close()
     def leave_group():
@@ -470,37 +547,6 @@ def main():
     if rank != 0:
         leave_group()
         return
-    n_stamped = sum(1 for i in range(args.steps) if i % 8 in (0, 3))
-    table_timed = kernel_table(timed_tags, rows, B, n_stamped)
-    d0 = table_timed.get(dom, table[dom])                           # measured over the timed region itself
-    tj, tsrc = {}, None
-    for rnd in ("r06", "r05", "r04", "r03", "r02"):                 # this round's PMC passes (tools/collect_profiles.sh)
-        tpath = os.path.join(ROOT, "profiles", "%s_traffic.json" % rnd)
-        if os.path.exists(tpath):
-            tj = json.load(open(tpath))
-            tsrc = "profiles/%s_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, not measured in this run)" % rnd
-            break
-    dom_split = "split" in dom and d0["bound"] == "mfma"
-    roof = {"bound": d0["bound"], "kernel": dom, "layers": d0["tags"],
-            # split-bf16 kernels: achieved = the bf16 term products the matrix pipe executed (6 per f32-equivalent product)
-            # against the dense bf16 peak; frac_f32_equiv prices the same launches' f32-equivalent FLOPs against the FP32-MFMA peak
-            "achieved": (d0.get("executed_bf16_tflops") if dom_split else d0["executed_tflops"]) if d0["bound"] == "mfma" else d0["algorithmic_gbps"],
-            "peak": (BF16_MFMA_PEAK if dom_split else FP32_MFMA_PEAK) / 1e12 if d0["bound"] == "mfma" else 8000.0,
-            "unit": "TFLOP/s" if d0["bound"] == "mfma" else "GB/s", "frac": d0["frac"],
-            "frac_f32_equiv": d0.get("frac_f32_equiv"), "f32_equiv_tflops": d0["executed_tflops"] if d0["bound"] == "mfma" else None,
-            "arithmetic": "split-bf16 (6 bf16 x bf16 term products per f32 product, f32 accumulate)" if "split" in dom else "f32 MFMA",
-            "traffic": (tj.get(dom) or tj.get(dom.split("<")[0]) or tj.get(dom.split("<")[0].replace("_kernel", "_split_kernel")) or {}).get("bytes_per_launch"), "traffic_source": tsrc,
-            "kernel_avg_us": d0["kernel_avg_us"], "launches_per_step": d0["launches_per_step"],
-            "ms_per_step": d0["ms_per_step"], "dense_equiv_tflops": d0["dense_equiv_tflops"],
-            "frac_alone": table_alone.get(dom, {}).get("frac"), "kernel_avg_us_alone": table_alone.get(dom, {}).get("kernel_avg_us"),
-            "how": "in-kernel wall-clock stamps (gad_timing_slot) of every launch of the symbol on %d of the %d timed steps (the symbol "
-                   "was chosen from a %d-step probe of every tagged launch); executed FLOPs = de-duplicated rows (sa1 %d, "
-                   "sa2 %d, sa3 %d) x K x N x 2 per layer" % (n_stamped, args.steps, probe_n, rows["sa1"], rows["sa2"], rows["sa3"])}
-    # the five largest symbols of the step in the same units (the driver's record keeps `roofline`, not the top-level `kernels` table)
-    roof["by_kernel"] = [dict(kernel=k, bound=v["bound"], ms_per_step=v["ms_per_step"], launches_per_step=v["launches_per_step"],
-                              kernel_avg_us=v["kernel_avg_us"], frac=v["frac"], frac_f32_equiv=v.get("frac_f32_equiv"),
-                              kernel_avg_us_alone=table_alone.get(k, {}).get("kernel_avg_us"))
-                         for k, v in sorted(priced.items(), key=lambda kv: -kv[1]["ms_per_step"])[:5]]
     steps_per_s = args.steps * 1.0 / dt
     # whole-job aggregate: every rank processes one B=256 minibatch per optimiser step (weak scaling), so the job does
     # world x (B=256 minibatch-steps) per iteration; at N=1 this is the plain step rate
@@ -512,15 +558,47 @@ def main():
                       "batch_per_gpu": B, "global_batch": B * world, "points": 1024,
                       "parallelism": "dp%d" % world, "iterations_per_s": steps_per_s, "mfma_split": split_mode,
                       "enqueue": "run-ahead (update_parameters(sync=False), all steps complete at the closing fence)",
-                      "iterations_per_s_sync_each_step": rate_sync, "iterations_per_s_sync_prefetch_next": rate_sync_prefetch,
                       "value_definition": "B=%d minibatch gradient steps per second summed over ranks (= iterations/s x n_gpus)" % B, "inputs": "HBM-resident ring of %d pre-sampled minibatches" % args.ring},
-           "losses": {k: out[k] for k in ("critic_loss", "bc_loss", "actor_critic_loss")},
-           "roofline": roof}
+           "losses": {k: out[k] for k in ("critic_loss", "bc_loss", "actor_critic_loss")}}
+    if args.full:
+        n_stamped = sum(1 for i in range(args.steps) if i % 8 in (0, 3))
+        table_timed = kernel_table(timed_tags, rows, B, n_stamped)
+        d0 = table_timed.get(dom, table[dom])                           # measured over the timed region itself
+        tj, tsrc = {}, None
+        for rnd in ("r06", "r05", "r04", "r03", "r02"):                 # this round's PMC passes (tools/collect_profiles.sh)
+            tpath = os.path.join(ROOT, "profiles", "%s_traffic.json" % rnd)
+            if os.path.exists(tpath):
+                tj = json.load(open(tpath))
+                tsrc = "profiles/%s_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, not measured in this run)" % rnd
+                break
+        dom_split = "split" in dom and d0["bound"] == "mfma"
+        roof = {"bound": d0["bound"], "kernel": dom, "layers": d0["tags"],
+                # split-bf16 kernels: achieved = the bf16 term products the matrix pipe executed (6 per f32-equivalent product)
+                # against the dense bf16 peak; frac_f32_equiv prices the same launches' f32-equivalent FLOPs against the FP32-MFMA peak
+                "achieved": (d0.get("executed_bf16_tflops") if dom_split else d0["executed_tflops"]) if d0["bound"] == "mfma" else d0["algorithmic_gbps"],
+                "peak": (BF16_MFMA_PEAK if dom_split else FP32_MFMA_PEAK) / 1e12 if d0["bound"] == "mfma" else 8000.0,
+                "unit": "TFLOP/s" if d0["bound"] == "mfma" else "GB/s", "frac": d0["frac"],
+                "frac_f32_equiv": d0.get("frac_f32_equiv"), "f32_equiv_tflops": d0["executed_tflops"] if d0["bound"] == "mfma" else None,
+                "arithmetic": "split-bf16 (6 bf16 x bf16 term products per f32 product, f32 accumulate)" if "split" in dom else "f32 MFMA",
+                "traffic": (tj.get(dom) or tj.get(dom.split("<")[0]) or tj.get(dom.split("<")[0].replace("_kernel", "_split_kernel")) or {}).get("bytes_per_launch"), "traffic_source": tsrc,
+                "kernel_avg_us": d0["kernel_avg_us"], "launches_per_step": d0["launches_per_step"],
+                "ms_per_step": d0["ms_per_step"], "dense_equiv_tflops": d0["dense_equiv_tflops"],
+                "frac_alone": table_alone.get(dom, {}).get("frac"), "kernel_avg_us_alone": table_alone.get(dom, {}).get("kernel_avg_us"),
+                "how": "in-kernel wall-clock stamps (gad_timing_slot) of every launch of the symbol on %d of the %d timed steps (the symbol "
+                       "was chosen from a %d-step probe of every tagged launch); executed FLOPs = de-duplicated rows (sa1 %d, "
+                       "sa2 %d, sa3 %d) x K x N x 2 per layer" % (n_stamped, args.steps, probe_n, rows["sa1"], rows["sa2"], rows["sa3"])}
+        # the five largest symbols of the step in the same units (the driver's record keeps `roofline`, not the top-level `kernels` table)
+        roof["by_kernel"] = [dict(kernel=k, bound=v["bound"], ms_per_step=v["ms_per_step"], launches_per_step=v["launches_per_step"],
+                                  kernel_avg_us=v["kernel_avg_us"], frac=v["frac"], frac_f32_equiv=v.get("frac_f32_equiv"),
+                                  kernel_avg_us_alone=table_alone.get(k, {}).get("kernel_avg_us"))
+                             for k, v in sorted(priced.items(), key=lambda kv: -kv[1]["ms_per_step"])[:5]]
+        res["config"].update(iterations_per_s_sync_each_step=rate_sync, iterations_per_s_sync_prefetch_next=rate_sync_prefetch)
+        res["roofline"] = roof
     if dp_info is not None:
         res["config"].update(dp_info)
     # step-level view against the dense-FP32 roofline: mean 5.5078 GFLOP per sample and step
     res["step_dense_tflops"] = steps_per_s * world * B * 5.5078e9 / 1e12
-    if world == 1 and not args.no_host_rate:
+    if args.full and world == 1 and not args.no_host_rate:
         rng2 = np.random.default_rng(7)
         n = max(40, args.steps // 4)
         torch.cuda.synchronize()
@@ -578,9 +656,10 @@ def main():
         res["config"]["value_long"] = float(np.mean(rates[1 if split_mode else 0]))
         res["config"]["value_modes_note"] = ("alternating %d-step runs of the value loop in this process: f32-MFMA %s, split-bf16 %s steps/s"
                                              % (n_x, [round(v, 1) for v in rates[0]], [round(v, 1) for v in rates[1]]))
-    res["kernels"] = {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items() if kk != "tags"}
-                      for k, v in sorted(table.items(), key=lambda kv: -kv[1]["ms_per_step"])}
-    if world == 1 and not args.no_sa_kernel:
+    if args.full:
+        res["kernels"] = {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items() if kk != "tags"}
+                          for k, v in sorted(table.items(), key=lambda kv: -kv[1]["ms_per_step"])}
+    if args.full and world == 1 and not args.no_sa_kernel:
         # BASELINE.json's second metric, "SA-kernel HBM GB/s": the streaming set-abstraction kernels of THIS workload (HBM-bound:
         # 0.5-1 KB moved per row) from the table above -- inside the overlapped step and alone -- plus the materialising
         # configs[3] kernel behind pointnet2_utils.query_and_group
@@ -606,7 +685,7 @@ def main():
                                             "sa1_streaming_in_step": {k: {"gbps": v["achieved"], "frac": v["frac"], "us": v["kernel_avg_us"]}
                                                                       for k, v in sa.items() if k != "query_and_group"}}
         res["roofline"]["sa_kernel_mfma"] = {k: sm.get(k) for k in sm if not isinstance(sm.get(k), (dict, list))}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(cfg, host_batches[0], np.random.default_rng(3).random((B, 6)).astype(np.float32))
     else:
         res["cpu_baseline"] = None

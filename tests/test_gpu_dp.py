@@ -218,7 +218,7 @@ def test_bench_launches_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, GAD_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "2",
                           "--batch", "32", "--buffer", "1500", "--probe-steps", "2", "--no-cpu-baseline", "--no-host-rate",
                           "--no-sa-kernel"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]

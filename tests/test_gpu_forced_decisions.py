@@ -10,6 +10,7 @@ from tests.helpers import assert_close
 
 pytestmark = pytest.mark.gpu
 SKIP = (".1.0.bias", ".1.3.bias")          # biases in front of a train-mode BatchNorm: analytically zero gradient
+FEW = 16                                   # tensors with fewer entries: typical error = root mean square, not median
 
 
 @pytest.mark.parametrize("B,seed,policy_step", [(32, 1, False), (64, 2, False), (32, 3, True), (256, 4, False)])
@@ -86,7 +87,10 @@ def test_step_gradients_with_forced_decisions(B, seed, policy_step):
         mine = dict(nets[nn].named_parameters())[n].grad.double().cpu()
         scale = float(ref.abs().max()) + 1e-300
         eh, e3 = (mine - ref).abs() / scale, (g32[key] - ref).abs() / scale
-        row = (float(eh.median()), float(eh.max()), float(e3.median()), float(e3.max()))
+        # the typical error: the median; for a tensor of a handful of entries (policy/mean.bias: 6) the median is one of them and
+        # torch's float32 yardstick for it moved 2e-6 .. 2e-5 with the CPU thread count of the host: root mean square for both
+        typ = (lambda e: float(e.pow(2).mean().sqrt())) if ref.numel() < FEW else (lambda e: float(e.median()))
+        row = (typ(eh), float(eh.max()), typ(e3), float(e3.max()))
         lines.append("%-64s %10.3e %10.2e %10.2e %10.2e %10.2e" % ((key, scale) + row))
         # as accurate as torch's own float32 evaluation of the same smooth function (x3), floors at float32 resolution of a
         # sum of ~1e5 cancelling terms

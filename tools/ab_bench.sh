@@ -4,7 +4,7 @@ REPS=${REPS:-2}
 STEPS=${STEPS:-100}
 for rep in $(seq $REPS); do
   for cfg in "$@"; do
-    env $cfg python bench.py --steps $STEPS --warmup 20 --no-sa-kernel --no-cpu-baseline --no-host-rate --probe-steps 2 2>/dev/null | \
+    env $cfg python bench.py --full --steps $STEPS --warmup 20 --no-sa-kernel --no-cpu-baseline --no-host-rate --probe-steps 2 2>/dev/null | \
       CFG="$cfg" python -c "
 import json,sys,os
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -1,4 +1,4 @@
-run() { env "$@" python bench.py --steps 200 --warmup 30 --no-cpu-baseline --no-host-rate --no-sa-kernel 2>/tmp/err.txt | tail -1 | python -c "import sys,json; r=json.loads(sys.stdin.read()); print('$*', round(r['value'],1), round(r['config']['iterations_per_s_sync_each_step'],1))" || tail -3 /tmp/err.txt; }
+run() { env "$@" python bench.py --full --steps 200 --warmup 30 --no-cpu-baseline --no-host-rate --no-sa-kernel 2>/tmp/err.txt | tail -1 | python -c "import sys,json; r=json.loads(sys.stdin.read()); print('$*', round(r['value'],1), round(r['config']['iterations_per_s_sync_each_step'],1))" || tail -3 /tmp/err.txt; }
 for i in 1 2; do
 run X=0
 run GAD_CU_MASK_C=128

@@ -6,7 +6,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-BENCH="python bench.py --no-cpu-baseline --no-host-rate --no-sa-kernel"
+BENCH="python bench.py --full --no-cpu-baseline --no-host-rate --no-sa-kernel"
 timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_stats -o r -- $BENCH --steps 50 --warmup 10 > $OUT/${R}_stats_bench.log 2>&1
 python tools/prof_summary.py /tmp/prof_stats 90 > $OUT/${R}_rocprofv3_kernel_stats_bench_B256.txt 2>&1
 timeout 900 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/prof_fetch -o r -- $BENCH --steps 6 --warmup 4 --probe-steps 2 > /dev/null 2>&1
@@ -22,5 +22,5 @@ timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/qg_fetch -o r -- p
 timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/qg_write -o r -- python tools/prof_query_and_group.py run > /dev/null 2>&1
 python tools/prof_query_and_group.py merge /tmp/qg_fetch /tmp/qg_write $OUT/${R}_traffic.json >> $OUT/${R}_traffic.txt 2>&1
 cp $OUT/${R}_traffic.json profiles/${R}_traffic.json 2>/dev/null     # bench.py reads roofline.traffic from here
-python bench.py --steps 200 --warmup 50 > $OUT/${R}_bench_B256.json 2> $OUT/${R}_bench_B256.err
+python bench.py --full --steps 200 --warmup 50 > $OUT/${R}_bench_B256.json 2> $OUT/${R}_bench_B256.err
 tail -c 600 $OUT/${R}_bench_B256.json

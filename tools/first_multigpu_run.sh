@@ -23,7 +23,7 @@ for N in 1 2 4 8; do
       [ $N -eq 1 ] && [ "$COMMS$BUCK" != "one0" ] && continue
       tag="n${N}_comms-${COMMS}_buckets-${BUCK}"
       echo "== 2. bench --gpus $N  GAD_DP_COMMS=$COMMS GAD_DP_BUCKETS=$BUCK"
-      GAD_DP_COMMS=$COMMS GAD_DP_BUCKETS=$BUCK timeout 1200 python bench.py --gpus $N --steps 100 --warmup 20 --no-cpu-baseline --no-sa-kernel \
+      GAD_DP_COMMS=$COMMS GAD_DP_BUCKETS=$BUCK timeout 1200 python bench.py --full --gpus $N --steps 100 --warmup 20 --no-cpu-baseline --no-sa-kernel \
         > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err
       line $tag < $OUT/bench_$tag.json | tee -a $OUT/summary.txt
     done

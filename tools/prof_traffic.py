@@ -37,7 +37,7 @@ def per_kernel(path, counter):
 def main(fetch_dir, write_dir, out):
     f, w = per_kernel(fetch_dir, "FETCH_SIZE"), per_kernel(write_dir, "WRITE_SIZE")
     res = {"_about": "HBM bytes per launch from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes of "
-                     "`python bench.py --steps 6 --warmup 4 --probe-steps 2 --no-cpu-baseline --no-host-rate --no-sa-kernel`, "
+                     "`python bench.py --full --steps 6 --warmup 4 --probe-steps 2 --no-cpu-baseline --no-host-rate --no-sa-kernel`, "
                      "B=256; kernels are serialised under --pmc); FETCH_SIZE doubled (gfx950: 16-byte coalesced loads are tallied "
                      "at half their size, MI355X_MICROARCH.md); KB = 1024 B; averaged over every launch of the symbol"}
     for k in sorted(set(f) & set(w), key=lambda k: -(2 * f[k][1] + w[k][1]) * f[k][0]):

@@ -7,7 +7,7 @@ for c in 0 1 0 1; do
   echo "== GAD_PLAN_C=$c host runahead"; GAD_PLAN_C=$c timeout 300 python tools/diag_host_runahead.py 2>&1 | tail -2
 done
 for c in 0 1 0 1; do
-  echo "== GAD_PLAN_C=$c bench"; GAD_PLAN_C=$c timeout 600 python bench.py --steps 200 --warmup 50 --no-cpu-baseline --no-sa-kernel 2>/dev/null | python -c "
+  echo "== GAD_PLAN_C=$c bench"; GAD_PLAN_C=$c timeout 600 python bench.py --full --steps 200 --warmup 50 --no-cpu-baseline --no-sa-kernel 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

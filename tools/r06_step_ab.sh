@@ -7,7 +7,7 @@ for c in "GAD_STEP_PLAN=0 GAD_PLAN_C=0" "GAD_STEP_PLAN=0 GAD_PLAN_C=1" "GAD_STEP
   echo "== $c host runahead"; env $c timeout 300 python tools/diag_host_runahead.py 2>&1 | tail -2
 done
 for c in "GAD_STEP_PLAN=0 GAD_PLAN_C=0" "GAD_STEP_PLAN=1 GAD_PLAN_C=1" "GAD_STEP_PLAN=0 GAD_PLAN_C=0" "GAD_STEP_PLAN=1 GAD_PLAN_C=1"; do
-  echo "== $c bench"; env $c timeout 600 python bench.py --steps 200 --warmup 50 --no-cpu-baseline --no-sa-kernel 2>/dev/null | python -c "
+  echo "== $c bench"; env $c timeout 600 python bench.py --full --steps 200 --warmup 50 --no-cpu-baseline --no-sa-kernel 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
