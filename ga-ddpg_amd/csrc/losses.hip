@@ -54,15 +54,18 @@ __device__ __forceinline__ float goal_point_loss(const float* q, const float* t,
     return loss;
 }
 
-// head aux output x (7 raw) -> [normalize(x[:4]), x[4:]]   (F.normalize eps 1e-12)
+// head aux output x (7 raw) -> [normalize(x[:4]), x[4:]]   (F.normalize eps 1e-12); returns the unclamped norm
 __device__ __forceinline__ float unit_quat(const float* x, float* q) {
-    const float n = fmaxf(sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3]), 1e-12f);
+    const float r = sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3]);
+    const float n = fmaxf(r, 1e-12f);
     for (int i = 0; i < 4; ++i) q[i] = x[i] / n;
-    return n;
+    return r;
 }
-// gradient through the normalisation: (g - q (q.g)) / n
-__device__ __forceinline__ void unit_quat_bwd(const float* q, float n, const float* gq, float* gx) {
-    const float d = q[0] * gq[0] + q[1] * gq[1] + q[2] * gq[2] + q[3] * gq[3];
+// gradient through the normalisation x / max(|x|, 1e-12) at the unclamped norm r: (g - q (q.g)) / |x|; below the clamp the
+// denominator is a constant (torch's clamp_min passes no gradient there): g / 1e-12
+__device__ __forceinline__ void unit_quat_bwd(const float* q, float r, const float* gq, float* gx) {
+    const float d = r < 1e-12f ? 0.f : q[0] * gq[0] + q[1] * gq[1] + q[2] * gq[2] + q[3] * gq[3];
+    const float n = fmaxf(r, 1e-12f);
     for (int i = 0; i < 4; ++i) gx[i] = (gq[i] - q[i] * d) / n;
 }
 
@@ -107,14 +110,14 @@ __global__ __launch_bounds__(256) void critic_loss_kernel(const float* __restric
             g[h] = keep ? (ad < 1.f ? d : sgn(d)) * inv_k : 0.f;
         }
         float q[4], gq[4], gt[3], gx[4];
-        const float n = unit_quat(o + 2, q);
+        const float r = unit_quat(o + 2, q);
         if (aux_norm) {
             for (int c = 0; c < 4; ++c) aux_norm[(size_t)i * 7 + c] = q[c];
             for (int c = 0; c < 3; ++c) aux_norm[(size_t)i * 7 + 4 + c] = o[6 + c];
         }
         if (critic_aux && ret[i] > 0.f) {
             la += goal_point_loss(q, o + 6, goal + (size_t)i * 7, goal + (size_t)i * 7 + 4, gq, gt);
-            unit_quat_bwd(q, n, gq, gx);
+            unit_quat_bwd(q, r, gq, gx);
             for (int c = 0; c < 4; ++c) g[2 + c] = gx[c] * inv_g;
             for (int c = 0; c < 3; ++c) g[6 + c] = gt[c] * inv_g;
         } else {
@@ -305,17 +308,18 @@ __global__ __launch_bounds__(256) void actor_loss_kernel(const float* __restrict
             lb += bc_point_loss(p, expert_action + (size_t)i * 6, ga);
             for (int c = 0; c < 6; ++c) gpi[c] += ga[c] * inv_e * bc_scale;
         }
-        for (int c = 0; c < 6; ++c) {                      // pi = tanh(m)*scale
-            const float th = p[c] / ascale[c];
+        for (int c = 0; c < 6; ++c) {                      // pi = tanh(m)*scale + bias: dpi/dm = scale*(1 - tanh(m)^2)
+            const float th = tanhf(o[c]);                  // (from the raw mean: pi/scale carries the bias)
             g[c] = gpi[c] * ascale[c] * (1.f - th * th);
         }
         if (policy_aux && ret[i] > 0.f) {                  // policy_aux implies pitch >= 13 (checked by the host entry)
             float q[4], gq[4], gt[3], gx[4];
-            const float n = unit_quat(o + 6, q);
+            const float r = unit_quat(o + 6, q);
             la += goal_point_loss(q, o + 10, goal + (size_t)i * 7, goal + (size_t)i * 7 + 4, gq, gt);
-            unit_quat_bwd(q, n, gq, gx);
+            unit_quat_bwd(q, r, gq, gx);
             for (int c = 0; c < 4; ++c) g[6 + c] = gx[c] * inv_g;
             for (int c = 0; c < 3; ++c) g[10 + c] = gt[c] * inv_g;
+            for (int c = 13; c < pitch; ++c) g[c] = 0.f;   // columns past the aux head: no loss term
         } else {
             for (int c = 6; c < pitch; ++c) g[c] = 0.f;
         }

@@ -443,7 +443,10 @@ int gad_critic_loss(const float* out9, const float* tgt_out9, const float* rewar
  * -ratio*mean(min(q1_pi,q2_pi)) wrt pi arriving as g_pi_critic (B,6) (already scaled).
  *   g_pol13 receives dLoss/d(pol13); scalars[0]=bc_loss (scaled), [1]=policy_grasp_aux_loss.     */
 /* `pitch` = floats per row of the head output / gradient buffers: 6 + extra_pred_dim (13 with policy_aux, 7
- * without: reference core/agent.py:31-36); aux_norm / policy_aux need pitch >= 13.                */
+ * without: reference core/agent.py:31-36); aux_norm / policy_aux need pitch >= 13.  gad_actor_loss writes every column
+ * of g_pol13 for every row: columns without a loss term (6 .. pitch-1 without policy_aux or on rows with return <= 0,
+ * 13 .. pitch-1 with it) receive 0, so a pitch above 13 is accepted and its extra columns are zeroed.  The chain into
+ * the raw means is scale * (1 - tanh(mean)^2), taken from pol13 (not from pi, which carries the bias).            */
 int gad_policy_outputs(const float* pol13, int B, int pitch, const float* action_scale, const float* action_bias /*nullable*/,
                        float* pi, float* aux_norm /*nullable*/, void* stream);
 int gad_actor_loss(const float* pol13, const float* pi, const float* expert_action,

@@ -13,11 +13,22 @@ SKIP = (".1.0.bias", ".1.3.bias")          # biases in front of a train-mode Bat
 FEW = 16                                   # tensors with fewer entries: typical error = root mean square, not median
 
 
-@pytest.mark.parametrize("B,seed,policy_step", [(32, 1, False), (64, 2, False), (32, 3, True), (256, 4, False)])
-def test_step_gradients_with_forced_decisions(B, seed, policy_step):
+def _space(name):
+    """None: the reference's PandaTaskSpace6D (symmetric bounds); "asym": oracle.detfill.AsymTaskSpace6D, whose bias reaches
+    pi = tanh(mean) * scale + bias and the chain factor of the actor / BC gradient"""
+    from oracle.detfill import AsymTaskSpace6D
+    return AsymTaskSpace6D() if name == "asym" else None
+
+
+@pytest.mark.parametrize("B,seed,policy_step,space", [
+    pytest.param(32, 1, False, None, id="32-1-False"), pytest.param(64, 2, False, None, id="64-2-False"),
+    pytest.param(32, 3, True, None, id="32-3-True"), pytest.param(256, 4, False, None, id="256-4-False"),
+    pytest.param(32, 1, False, "asym", id="32-1-False-asym"), pytest.param(32, 3, True, "asym", id="32-3-True-asym")])
+def test_step_gradients_with_forced_decisions(B, seed, policy_step, space):
     """B = 256 is the bench size: there the row counts route the layers to other kernels than at B <= 64
     (wide tiles instead of 64 x 64 tiles for SA2 / SA3, the fused streaming backward for SA1) -- every gradient tensor is held
-    to the same criterion against the float64 oracle (two ~30 - 60 s CPU steps: float64 and float32 with the HIP decisions)."""
+    to the same criterion against the float64 oracle (two ~30 - 60 s CPU steps: float64 and float32 with the HIP decisions).
+    space "asym": asymmetric action bounds on both sides (the policy and the target policy carry action_bias)."""
     from ga_ddpg_amd.core.replay_memory import BaseMemory
     from ga_ddpg_amd.experiments.config import load_cfg
     from ga_ddpg_amd.synth_data import fill_synthetic_buffer, sample_valid_batch
@@ -31,7 +42,7 @@ def test_step_gradients_with_forced_decisions(B, seed, policy_step):
     rng = np.random.default_rng(seed)
     batch = sample_valid_batch(mem, B, rng)
     u = rng.random((B, 6)).astype(np.float32)
-    agent, nets = _filled_agent("ddpg_td3_aux.yaml", 3)
+    agent, nets = _filled_agent("ddpg_td3_aux.yaml", 3, _space(space))
     agent.update_step = 1                                  # no actor-critic term: slot_v still holds the critic-phase value pass
     got = agent.update_parameters(batch, agent.update_step, 0, noise_u=u)
     torch.cuda.synchronize()
@@ -42,7 +53,7 @@ def test_step_gradients_with_forced_decisions(B, seed, policy_step):
     if policy_step:
         # the critic phase is the same computation on either kind of step: its decisions come from the run above; a twin
         # agent then takes the policy step, whose slots end up holding the policy pass and the Q(s, pi(s)) value pass
-        agent, nets = _filled_agent("ddpg_td3_aux.yaml", 3)
+        agent, nets = _filled_agent("ddpg_td3_aux.yaml", 3, _space(space))
         agent.update_step = 2
         got = agent.update_parameters(batch, agent.update_step, 0, noise_u=u)
         torch.cuda.synchronize()
@@ -56,6 +67,9 @@ def test_step_gradients_with_forced_decisions(B, seed, policy_step):
         o = ref_step.OracleAgent(c.RL_TRAIN)
         for n, net in o.nets().items():
             fill_module_(net, n, 3)
+        if space is not None:      # (before the dtype change: float32 buffers, as the HIP side holds them)
+            o.policy.set_action_space(_space(space))
+            o.policy_target.set_action_space(_space(space))
         o.to_dtype(dtype)
         o.update_step = step
         with forced_forward(o.state_feature_extractor.module, dec) as ff:
@@ -78,7 +92,7 @@ def test_step_gradients_with_forced_decisions(B, seed, policy_step):
         eh = np.abs(mine.cpu().numpy() - ref).max() / scale
         print("%-10s max err / max|ref|: hip %.2e   oracle-f32 %.2e" % (what, eh, e32))
         assert eh <= max(3 * e32, 2e-5), (what, eh, e32)
-    lines = ["%-64s %10s %10s %10s %10s %10s" % ("tensor (B=%d%s, forced decisions)" % (B, ", policy step" if policy_step else ""), "max|f64|", "hip med", "hip max", "f32 med", "f32 max")]
+    lines = ["%-64s %10s %10s %10s %10s %10s" % ("tensor (B=%d%s%s, forced decisions)" % (B, ", policy step" if policy_step else "", ", asymmetric bounds" if space else ""), "max|f64|", "hip med", "hip max", "f32 med", "f32 max")]
     bad = []
     for key, ref in sorted(g64.items()):
         nn, n = key.split("/", 1)
@@ -101,13 +115,15 @@ def test_step_gradients_with_forced_decisions(B, seed, policy_step):
     if os.path.isdir(out_dir):
         from ga_ddpg_amd import hip as _hip
         mode = "_split" if _hip.get_option("mfma_split") else "_f32mfma"          # (both arithmetic modes: tests/conftest.py BOTH_MODES)
-        open(os.path.join(out_dir, "grad_accuracy_forced_B%d%s%s.txt" % (B, "_policy_step" if policy_step else "", mode)), "w").write("\n".join(lines) + "\n")
+        open(os.path.join(out_dir, "grad_accuracy_forced_B%d%s%s%s.txt" % (B, "_policy_step" if policy_step else "", "_asym" if space else "", mode)), "w").write("\n".join(lines) + "\n")
     assert len(lines) > (35 if policy_step else 90)
     assert not bad, "\n".join([lines[0]] + bad)
 
 
-def test_bc_step_gradients_with_forced_decisions():
-    """the behaviour-cloning step of BASELINE configs[0] (B = 64): one policy pass forward + backward, same tight criterion"""
+@pytest.mark.parametrize("space", [None, "asym"], ids=["symmetric", "asym"])
+def test_bc_step_gradients_with_forced_decisions(space):
+    """the behaviour-cloning step of BASELINE configs[0] (B = 64): one policy pass forward + backward, same tight criterion;
+    space "asym": asymmetric action bounds (the BC gradient's chain factor through pi = tanh(mean) * scale + bias)"""
     from ga_ddpg_amd.core.replay_memory import BaseMemory
     from ga_ddpg_amd.experiments.config import load_cfg
     from ga_ddpg_amd.synth_data import fill_synthetic_buffer, sample_valid_batch
@@ -120,7 +136,7 @@ def test_bc_step_gradients_with_forced_decisions():
     mem = BaseMemory(2000, c, point_dtype=np.float32)
     fill_synthetic_buffer(mem, 2000, seed=11)
     batch = sample_valid_batch(mem, B, np.random.default_rng(4))
-    agent, nets = _filled_agent("bc_dagger_aux.yaml", 3)
+    agent, nets = _filled_agent("bc_dagger_aux.yaml", 3, _space(space))
     got = agent.update_parameters(batch, agent.update_step, 0)
     torch.cuda.synchronize()
     rt = agent._rt
@@ -130,6 +146,9 @@ def test_bc_step_gradients_with_forced_decisions():
         o = ref_step.OracleAgent(c.RL_TRAIN)
         for n, net in o.nets().items():
             fill_module_(net, n, 3)
+        if space is not None:
+            o.policy.set_action_space(_space(space))
+            o.policy_target.set_action_space(_space(space))
         o.to_dtype(dtype)
         with forced_forward(o.state_feature_extractor.module, dec) as ff:
             out = o.update_bc(batch)
@@ -146,7 +165,7 @@ def test_bc_step_gradients_with_forced_decisions():
         eh = np.abs(mine.cpu().numpy() - ref).max() / scale
         e32 = np.abs(o32.dbg[key].double().numpy() - ref).max() / scale
         assert eh <= max(3 * e32, 2e-5), (key, eh, e32)
-    lines = ["%-64s %10s %10s %10s %10s %10s" % ("tensor (BC step, B=64, forced decisions)", "max|f64|", "hip med", "hip max", "f32 med", "f32 max")]
+    lines = ["%-64s %10s %10s %10s %10s %10s" % ("tensor (BC step, B=64%s, forced decisions)" % (", asymmetric bounds" if space else ""), "max|f64|", "hip med", "hip max", "f32 med", "f32 max")]
     bad = []
     for key, ref in sorted(g64.items()):
         nn, n = key.split("/", 1)
@@ -164,7 +183,7 @@ def test_bc_step_gradients_with_forced_decisions():
     if os.path.isdir(out_dir):
         from ga_ddpg_amd import hip as _hip
         mode = "_split" if _hip.get_option("mfma_split") else "_f32mfma"
-        open(os.path.join(out_dir, "grad_accuracy_forced_BC_B64%s.txt" % mode), "w").write("\n".join(lines) + "\n")
+        open(os.path.join(out_dir, "grad_accuracy_forced_BC_B64%s%s.txt" % ("_asym" if space else "", mode)), "w").write("\n".join(lines) + "\n")
     assert len(lines) > 30
     assert not bad, "\n".join([lines[0]] + bad)
 

@@ -15,10 +15,10 @@ SEED = 1234
 SKIP = (".1.0.bias", ".1.3.bias")     # biases in front of a train-mode BN: zero gradient analytically
 
 
-def _filled_agent(cfg_name, seed):
+def _filled_agent(cfg_name, seed, action_space=None):
     from ga_ddpg_amd.api import make_agent
     from oracle.detfill import fill_module_
-    agent, cfg = make_agent(cfg_name)
+    agent, cfg = make_agent(cfg_name, action_space=action_space)
     nets = {"policy": agent.policy, "policy_target": agent.policy_target,
             "state_feature_extractor": agent.state_feature_extractor}
     if hasattr(agent, "critic"):

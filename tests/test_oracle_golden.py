@@ -44,6 +44,27 @@ def test_losses_and_noise(golden_dir):
     assert (g["noise_delta"] < 0).all()
 
 
+def test_float64_loss_references_reproduce_golden(golden_dir):
+    """The yardstick of tests/test_gpu_head_losses.py: goal_pred_loss, pose_bc_loss and target_noise evaluated in float64 on
+    the golden inputs reproduce the reference's own float32 results (core/loss.py, core/utils.py get_noise_delta) to float32
+    rounding: 4 ulp (2.4e-7) of the value for the losses and noise, of the tensor's max for the gradients."""
+    f32 = 2.0 ** -22
+    g = np.load(os.path.join(golden_dir, "losses.npz"))
+    d64 = lambda k: torch.tensor(g[k], dtype=torch.float64)
+    pred = d64("goal_pred").requires_grad_(True)
+    l = ref_step.goal_pred_loss(pred, d64("goal_gt"))
+    l.backward()
+    assert_close(l.item(), g["goal_loss"], f32, 0, "goal loss (float64)")
+    assert_close(pred.grad.numpy(), g["goal_grad"], 0, f32 * np.abs(pred.grad.numpy()).max(), "goal grad (float64)")
+    pi = d64("bc_pi").requires_grad_(True)
+    l2 = ref_step.pose_bc_loss(pi, d64("bc_act"))
+    l2.backward()
+    assert_close(l2.item(), g["bc_loss"], f32, 0, "bc loss (float64)")
+    assert_close(pi.grad.numpy(), g["bc_grad"], 0, f32 * np.abs(pi.grad.numpy()).max(), "bc grad (float64)")
+    d = ref_step.target_noise(d64("noise_u").clone(), float(g["noise_level"]))
+    assert_close(d.numpy(), g["noise_delta"], f32, 0, "noise (float64)")
+
+
 def test_heads(golden_dir):
     g = np.load(os.path.join(golden_dir, "heads.npz"))
     x = torch.tensor(g["x"])
