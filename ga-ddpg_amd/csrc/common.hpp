@@ -42,6 +42,22 @@ unsigned long long* gad_take_timing_slot();
 unsigned long long* gad_take_timing_slot(void* stream);
 int gad_take_grid_rows();       // rows the caller expects to be live (0: unknown) -- sizes the grid of the next tile launch
 
+// ---- deterministic mode (library option "deterministic", gemm.hip; include/gaddpg.h gad_set_option) ----
+// 1: every entry point's result is independent of the launch grid, grid-rows hints, stream interleaving and timing: per-workgroup
+// partials go to slots indexed by a grid-independent unit and are summed in slot order by gad_ordered_reduce (no float atomics
+// whose order decides the rounding).
+int gad_deterministic();
+// library-owned device scratch of the mode, one buffer per (stream, kind): allocated on first use, grown when a call needs more, held
+// until the option is switched off (gad_set_option("deterministic", 0) frees them all); NULL with the error set on failure.
+// Stream-ordered: a buffer serves one launch sequence at a time.  Growing synchronises the stream and calls hipFree / hipMalloc
+// inside the entry point: not legal while a graph is being captured (nothing captures here; a capturing caller must run one
+// uncaptured call per shape first).
+enum { GAD_DET_SLOTS = 0, GAD_DET_ROWS = 1, GAD_DET_SLOTS2 = 2, GAD_DET_RUNS = 3 };
+void* gad_det_scratch(void* stream, int kind, size_t bytes);
+// out[c] += sum_{s = 0 .. nslots-1, ascending} slots[s * slot_stride + c]  (f64), for c < ncols: ONE add per element and launch
+int gad_ordered_reduce(const float* slots, long long slot_stride, int nslots, long long ncols, double* out, void* stream);
+int gad_ordered_reduce(const double* slots, long long slot_stride, int nslots, long long ncols, double* out, void* stream);
+
 // Train-mode BatchNorm finalisation of a layer (internal argument blocks of bn_finalize_kernel / bn_bwd_coef_kernel /
 // the pool finalisation; not part of the C ABI).
 struct gad_bn_fin {

@@ -19,6 +19,7 @@
 // BatchNorm statistics: registers -> __shfl_xor -> LDS across wavefronts -> f64 device atomics
 // into one of GAD_STAT_REPLICAS accumulators (blockIdx % replicas) to bound same-address contention.
 #include "common.hpp"
+#include <mutex>
 #include <type_traits>
 #include <string.h>
 
@@ -549,8 +550,9 @@ struct Groups {
     int n; int aoff[GAD_MAX_GROUPS]; int woff[GAD_MAX_GROUPS]; int ooff[GAD_MAX_GROUPS]; int nout[GAD_MAX_GROUPS];
 };
 
-// per-column partial sums held by lanes 0..31 of each wavefront -> one f64 atomic per column and block
-template <int WM, int WN, int TN>
+// per-column partial sums held by lanes 0..31 of each wavefront -> one f64 atomic per column and block (STORE: the deterministic
+// mode's plain store of the block's partial into its own slot, out0 / out1 = that slot)
+template <int WM, int WN, int TN, bool STORE = false>
 __device__ __forceinline__ void block_column_atomics(float* red, const float (&c0)[TN], const float (&c1)[TN], int lane,
                                                      int wm, int wn, int col0, int col_limit, double* out0,
                                                      double* out1) {
@@ -572,15 +574,21 @@ __device__ __forceinline__ void block_column_atomics(float* red, const float (&c
         float s0 = 0.f, s1 = 0.f;
 #pragma unroll
         for (int w = 0; w < WM; ++w) { s0 += red[w * BN + tid]; s1 += red[(WM + w) * BN + tid]; }
-        atomic_add_f64(out0 + col0 + tid, (double)s0);
-        atomic_add_f64(out1 + col0 + tid, (double)s1);
+        if (STORE) {
+            out0[col0 + tid] = (double)s0;
+            out1[col0 + tid] = (double)s1;
+        } else {
+            atomic_add_f64(out0 + col0 + tid, (double)s0);
+            atomic_add_f64(out1 + col0 + tid, (double)s1);
+        }
     }
 }
 
 // ------------------------------------------------------------------------------------------------
 // forward:  zout[r][n] = sum_k X[r][k] * W[n][k]      (+ weighted BatchNorm statistics)
 // ------------------------------------------------------------------------------------------------
-template <int WM, int WN, int TM, int TN, int XM, bool POOL>
+// DET (deterministic mode): stat_sum / stat_sq are slot planes of stat_stride doubles per block; block x stores its partial in row x
+template <int WM, int WN, int TM, int TN, int XM, bool POOL, bool DET = false>
 __global__ __launch_bounds__(256) void gemm_fwd_kernel(XSrc x, Groups gr, const int32_t* __restrict__ n_rows_dev,
                                                         int n_rows_static, const float* __restrict__ row_w,
                                                         const float* __restrict__ W, int Kp,
@@ -732,10 +740,10 @@ __global__ __launch_bounds__(256) void gemm_fwd_kernel(XSrc x, Groups gr, const 
         __syncthreads();   // wS / ptS reuse
     }
     if (stat_sum) {
-        const int rep = blockIdx.x % GAD_STAT_REPLICAS;
-        block_column_atomics<WM, WN, TN>(smem, csum, csq, lane, wm, wn, n0, n_out,
-                                         stat_sum + (size_t)rep * stat_stride + ooff,
-                                         stat_sq + (size_t)rep * stat_stride + ooff);
+        const int rep = DET ? blockIdx.x : blockIdx.x % GAD_STAT_REPLICAS;
+        block_column_atomics<WM, WN, TN, DET>(smem, csum, csq, lane, wm, wn, n0, n_out,
+                                              stat_sum + (size_t)rep * stat_stride + ooff,
+                                              stat_sq + (size_t)rep * stat_stride + ooff);
     }
 }
 
@@ -777,7 +785,10 @@ __device__ __forceinline__ gad_bf16x8 gad_as_bf16x8(gad_u32x4 u) { return *reint
 // on MI355X), GAD_OPT_mfma_split=0 keeps the f32 MFMA.  Precondition of the split form: finite operands below 3.39e38 in magnitude
 // (bf16(x) must not round to infinity; an infinite operand gives NaN where the f32 path gives +-inf).
 static int g_opt_mfma_split = 0;
-static bool split_on(int family) { return g_opt_mfma_split == GAD_SPLIT_ALL || (g_opt_mfma_split & family) != 0; }
+static int g_opt_deterministic = 0;       // option "deterministic": the generic tile kernels only, ordered partial sums (below gad_set_option)
+static bool split_on(int family) {
+    return !g_opt_deterministic && (g_opt_mfma_split == GAD_SPLIT_ALL || (g_opt_mfma_split & family) != 0);
+}
 
 // Wide-tile kernels in split form (gemm_fwd_wide / gemm_dx_wide with SP): a 64 x 128 block tile per 4-wavefront workgroup,
 // K-tile 32.  Both operand tiles live in LDS as three bf16 planes of 64-byte rows (32 reduction indices), double-buffered:
@@ -1152,7 +1163,7 @@ static int g_opt_dw_wide_wgs = 256;        // workgroups a wide-tile dW launch a
 // column), outputs a multiple of 128
 static bool fits_i32_bytes(long long rows, int pitch_a, int pitch_b, int pitch_c, int pitch_d);
 static bool fwd_wideable(const gad_gemm_fwd_args& a) {
-    if (!g_opt_fwd_wide || a.n_groups != 1 || a.zin_off[0] != 0 || a.w_off[0] != 0 || a.out_off[0] != 0) return false;
+    if (g_opt_deterministic || !g_opt_fwd_wide || a.n_groups != 1 || a.zin_off[0] != 0 || a.w_off[0] != 0 || a.out_off[0] != 0) return false;
     // (gathered input: the point-major feature tensor has at most as many rows as there are (group, point) rows upstream)
     if (!fits_i32_bytes(a.n_rows, a.mode == 1 ? a.feat_c : a.zin_pitch, a.zout ? a.zout_pitch : 0, 0, 0)) return false;
     if (a.n_rows < 2048 || a.n_out[0] % 128 != 0 || a.ones_col >= 0) return false;
@@ -1752,7 +1763,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_fwd_skinny_kernel(XSrc x, Groups
 static int g_opt_skinny_nw = SK_NW;    // wavefronts per skinny workgroup: 8, or 4 (A/B: a quarter of a CU's registers and < 60 KB of LDS, so a workgroup fits beside the side lanes' wide kernels)
 static int g_opt_fwd_skinny = 1, g_opt_dx_skinny = 1, g_opt_dx_stream = 1, g_opt_dw_skinny = 1, g_opt_dw_stream = 1;
 static bool fwd_skinny(const gad_gemm_fwd_args& a) {
-    return g_opt_fwd_skinny && a.mode == 0 && !a.n_rows_dev && a.n_rows <= 1024 && a.Kp <= SK_KCAP;
+    return !g_opt_deterministic && g_opt_fwd_skinny && a.mode == 0 && !a.n_rows_dev && a.n_rows <= 1024 && a.Kp <= SK_KCAP;
 }
 
 
@@ -1762,8 +1773,116 @@ static int g_opt_bwd_stream_wgs = DW_STREAM_SPLITS;   // persistent workgroups (
 static int g_opt_fwd_stream_wgs = 256;         // persistent workgroups of the streaming forward's layers 2 / 3 (A/B: fewer leave CUs to the sibling pass's small launches)
 static int g_opt_fwd_stream_l1_wgs = 256;      // persistent workgroups of the streaming forward's gathered first layer (A/B: 512 = two per CU)
 
+// ---- deterministic mode (option "deterministic"; include/gaddpg.h) ----
+// Routing: the generic tile kernels only (every family predicate below answers false, split-bf16 off, gad_gemm_bwd unfused); their
+// float atomics are replaced by stores of each workgroup's partial into a slot of its own (block index of a grid that depends on the
+// row CAPACITY only: grid-rows hints are ignored) and one ordered column reduce (ordered_reduce_kernel) that adds the slot sums, in
+// slot order, into replica 0 of the statistics or into the gradient arena.  The gathered first layers store each row's input
+// gradient and ordered kernels walk the rows: point-disjoint runs for dfeat, samples for daction.  No memory is allocated here.
+int gad_deterministic() { return g_opt_deterministic; }
+
+namespace {
+struct DetBuf { void* stream; int kind; void* p; size_t bytes; };
+std::mutex g_det_mu;
+DetBuf g_det_bufs[64];
+int g_det_n = 0;
+}  // namespace
+
+void* gad_det_scratch(void* stream, int kind, size_t bytes) {
+    std::lock_guard<std::mutex> lk(g_det_mu);
+    DetBuf* b = nullptr;
+    for (int i = 0; i < g_det_n; ++i)
+        if (g_det_bufs[i].stream == stream && g_det_bufs[i].kind == kind) b = &g_det_bufs[i];
+    if (!b) {
+        if (g_det_n == 64) { gad_set_error("deterministic mode: more than 64 scratch buffers (streams x kinds)"); return nullptr; }
+        b = &g_det_bufs[g_det_n++];
+        b->stream = stream; b->kind = kind; b->p = nullptr; b->bytes = 0;
+    }
+    if (b->bytes >= bytes) return b->p;
+    if (b->p) {                                          // earlier launches of this stream may still read it
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipFree(b->p) != hipSuccess) {
+            gad_set_error("deterministic mode: releasing a scratch buffer failed");
+            b->p = nullptr; b->bytes = 0;
+            return nullptr;
+        }
+        b->p = nullptr; b->bytes = 0;
+    }
+    size_t want = bytes + bytes / 4;                     // headroom: a slightly larger call does not reallocate
+    want = (want + 4095) & ~(size_t)4095;
+    if (hipMalloc(&b->p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        gad_set_error("deterministic mode: cannot allocate %zu bytes of scratch", want);
+        b->p = nullptr;
+        return nullptr;
+    }
+    b->bytes = want;
+    return b->p;
+}
+
+// the option's release path: switching the mode off frees every scratch buffer (hipFree waits for the work that uses them)
+static void det_scratch_release() {
+    std::lock_guard<std::mutex> lk(g_det_mu);
+    for (int i = 0; i < g_det_n; ++i)
+        if (g_det_bufs[i].p) (void)hipFree(g_det_bufs[i].p);
+    g_det_n = 0;
+}
+
+// the one reduce of the mode: thread = output element, slots summed in ascending order in f64, one add into out
+template <typename T>
+__global__ __launch_bounds__(256) void ordered_reduce_kernel(const T* __restrict__ slots, long long slot_stride, int nslots,
+                                                             long long ncols, double* __restrict__ out) {
+    const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (c >= ncols) return;
+    const T* p = slots + c;
+    double s = 0.0;
+    for (int i = 0; i < nslots; ++i) s += (double)p[(size_t)i * slot_stride];
+    atomic_add_f64(out + c, s);                          // the only add into this element in the launch
+}
+
+// the same sum for few columns over many slots (statistics, sums of squares): workgroup = column, thread t sums the slots
+// t, t + 256, ... in order, then a fixed pairwise tree over the 256 threads.  The order depends on nslots only.
+template <typename T>
+__global__ __launch_bounds__(256) void ordered_reduce_tree_kernel(const T* __restrict__ slots, long long slot_stride, int nslots,
+                                                                  double* __restrict__ out) {
+    __shared__ double red[256];
+    const long long c = blockIdx.x;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nslots; i += 256) s += (double)slots[(size_t)i * slot_stride + c];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomic_add_f64(out + c, red[0]);
+}
+
+template <typename T>
+static int ordered_reduce_launch(const T* slots, long long slot_stride, int nslots, long long ncols, double* out, void* stream) {
+    if (ncols <= 0 || nslots <= 0) return GAD_OK;
+    if (ncols <= 4096 && nslots > 256)                   // (the form is chosen by the shape alone)
+        hipLaunchKernelGGL(ordered_reduce_tree_kernel<T>, dim3((unsigned)ncols), dim3(256), 0, (hipStream_t)stream, slots, slot_stride,
+                           nslots, out);
+    else
+        hipLaunchKernelGGL(ordered_reduce_kernel<T>, dim3(gad_cdiv(ncols, 256)), dim3(256), 0, (hipStream_t)stream, slots, slot_stride,
+                           nslots, ncols, out);
+    GAD_CHECK_LAUNCH("ordered_reduce");
+    return GAD_OK;
+}
+int gad_ordered_reduce(const float* slots, long long slot_stride, int nslots, long long ncols, double* out, void* stream) {
+    return ordered_reduce_launch(slots, slot_stride, nslots, ncols, out, stream);
+}
+int gad_ordered_reduce(const double* slots, long long slot_stride, int nslots, long long ncols, double* out, void* stream) {
+    return ordered_reduce_launch(slots, slot_stride, nslots, ncols, out, stream);
+}
+
 extern "C" int gad_set_option(const char* name, int value) {
     GAD_REQUIRE(name, GAD_ERR_NULL, "set_option: null name");
+    if (!strcmp(name, "deterministic")) {
+        if (!value && g_opt_deterministic) det_scratch_release();
+        g_opt_deterministic = value ? 1 : 0;
+        return GAD_OK;
+    }
     if (!strcmp(name, "fwd_stream")) { g_opt_fwd_stream = value; return GAD_OK; }
     if (!strcmp(name, "bwd_stream_wgs")) { g_opt_bwd_stream_wgs = (value > 0 && value <= DW_STREAM_SPLITS) ? value : DW_STREAM_SPLITS; return GAD_OK; }
     if (!strcmp(name, "fwd_stream_wgs")) { g_opt_fwd_stream_wgs = value > 0 ? value : 256; return GAD_OK; }
@@ -1792,7 +1911,7 @@ extern "C" int gad_set_option(const char* name, int value) {
 
 // the streaming kernel covers: one group, no bias / extra column, Kp in {16, 64}, n_out in {64, 128}
 static bool fwd_streamable(const gad_gemm_fwd_args& a) {
-    if (!g_opt_fwd_stream) return false;
+    if (g_opt_deterministic || !g_opt_fwd_stream) return false;
     if (a.pool_key && !(a.mode == 0 && a.n_out[0] == 128)) return false;          // pooled instantiation: 64 -> 128 only
     if (a.n_groups != 1 || a.zin_off[0] != 0 || a.w_off[0] != 0 || a.out_off[0] != 0) return false;
     if (a.n_rows < 32768 || (a.n_out[0] != 64 && a.n_out[0] != 128) || (a.zout && a.zout_pitch != a.n_out[0])) return false;
@@ -1820,6 +1939,8 @@ static int max_nout(const Groups& g) { int m = 0; for (int i = 0; i < g.n; ++i) 
 
 static int check_input(const gad_gemm_fwd_args& a, const char* who) {
     if (a.mode == 2) {
+        GAD_REQUIRE(!g_opt_deterministic, GAD_ERR_UNSUPPORTED, "%s: mode 2 (recomputed 64-channel input) has no deterministic form "
+                    "(option \"deterministic\"): store the 64-channel input instead", who);
         GAD_REQUIRE(a.src_xyz && a.row_pt && a.row_grp && a.feat && a.pre_W, GAD_ERR_NULL, "%s: recomputed input needs the gather inputs and pre_W", who);
         GAD_REQUIRE(a.act_c == 0 || a.action, GAD_ERR_NULL, "%s: action", who);
         GAD_REQUIRE(fwd_streamable(a), GAD_ERR_SHAPE, "%s: mode 2 (recomputed 64-channel input) is a streaming-kernel form: SA1 rows, "
@@ -1837,6 +1958,22 @@ static int check_input(const gad_gemm_fwd_args& a, const char* who) {
         GAD_REQUIRE(a.act_c == 0 || a.action, GAD_ERR_NULL, "%s: action", who);
     }
     return GAD_OK;
+}
+
+// deterministic mode: zeroed slot planes (sum, square) of gx rows x ncol doubles for one statistics launch (blocks that return early
+// leave zeros), and their ordered sums into replica 0
+static double* det_stat_slots(int gx, int ncol, void* stream) {
+    const size_t n = 2 * (size_t)gx * ncol;
+    double* p = static_cast<double*>(gad_det_scratch(stream, GAD_DET_SLOTS, n * sizeof(double)));
+    if (p && hipMemsetAsync(p, 0, n * sizeof(double), (hipStream_t)stream) != hipSuccess) {
+        gad_set_error("deterministic mode: clearing the statistic slots failed");
+        return nullptr;
+    }
+    return p;
+}
+static int det_stat_reduce(const double* slots, int gx, int ncol, double* sum, double* sq, void* stream) {
+    if (int e = gad_ordered_reduce(slots, ncol, gx, ncol, sum, stream)) return e;
+    return gad_ordered_reduce(slots + (size_t)gx * ncol, ncol, gx, ncol, sq, stream);
 }
 
 extern "C" int gad_gemm_fwd(const gad_gemm_fwd_args* a, void* stream) {
@@ -1862,6 +1999,8 @@ extern "C" int gad_gemm_fwd(const gad_gemm_fwd_args* a, void* stream) {
                     a->n_out[0], rows);
     }
     const int grid_rows = (a->n_rows_dev && rows_hint > 0 && rows_hint < rows) ? rows_hint : rows;   // gad_grid_rows_hint
+    int ncol_stats = 0;                                  // deterministic mode: statistic columns this call covers (slot width)
+    for (int i = 0; i < gr.n; ++i) ncol_stats = gr.ooff[i] + gr.nout[i] > ncol_stats ? gr.ooff[i] + gr.nout[i] : ncol_stats;
     if (a->in_stat_sum) {
         GAD_REQUIRE(a->mode != 1 && a->n_groups == 1 && a->zin_off[0] == 0 && a->in_stat_sq && a->in_gamma && a->in_beta && a->scale && a->shift,
                     GAD_ERR_NULL, "gemm_fwd: input-layer BatchNorm block needs an ACT input, one group, in_stat_sq, in_gamma, in_beta, scale, shift");
@@ -1889,9 +2028,18 @@ extern "C" int gad_gemm_fwd(const gad_gemm_fwd_args* a, void* stream) {
     do {                                                                                                   \
         constexpr int BM = WM * TM * 32, BN = WN * TN * 32;                                                \
         int gx = gad_cdiv(grid_rows, BM); if (gx > GAD_GX_CAP) gx = GAD_GX_CAP;                                        \
-        hipLaunchKernelGGL((gemm_fwd_kernel<WM, WN, TM, TN, XM, POOL>), dim3(gx, gad_cdiv(nmax, BN), gr.n), dim3(256), \
-                           0, st, x, gr, a->n_rows_dev, rows, a->row_w, a->W, a->Kp, a->zout, a->zout_pitch, \
-                           a->stat_sum, a->stat_sq, a->stat_stride, pe, ts);                               \
+        if (g_opt_deterministic && a->stat_sum) {                                                          \
+            double* slots = det_stat_slots(gx, ncol_stats, stream);                                        \
+            if (!slots) return GAD_ERR_LAUNCH;                                                             \
+            hipLaunchKernelGGL((gemm_fwd_kernel<WM, WN, TM, TN, XM, POOL, true>), dim3(gx, gad_cdiv(nmax, BN), gr.n), dim3(256), \
+                               0, st, x, gr, a->n_rows_dev, rows, a->row_w, a->W, a->Kp, a->zout, a->zout_pitch, \
+                               slots, slots + (size_t)gx * ncol_stats, ncol_stats, pe, ts);                \
+            GAD_CHECK_LAUNCH("gemm_fwd");                                                                  \
+            if (int e_ = det_stat_reduce(slots, gx, ncol_stats, a->stat_sum, a->stat_sq, stream)) return e_; \
+        } else                                                                                             \
+            hipLaunchKernelGGL((gemm_fwd_kernel<WM, WN, TM, TN, XM, POOL>), dim3(gx, gad_cdiv(nmax, BN), gr.n), dim3(256), \
+                               0, st, x, gr, a->n_rows_dev, rows, a->row_w, a->W, a->Kp, a->zout, a->zout_pitch, \
+                               a->stat_sum, a->stat_sq, a->stat_stride, pe, ts);                           \
     } while (0)
 #define LAUNCH_FWD(WM, WN, TM, TN) do { if (a->mode == 0) LAUNCH_FWD2(WM, WN, TM, TN, 0, false); else LAUNCH_FWD2(WM, WN, TM, TN, 1, false); } while (0)
     if (fwd_streamable(*a)) {
@@ -1956,7 +2104,8 @@ struct DxEpi {
     float* dfeat; int feat_c; const int32_t* row_pt; const int32_t* row_grp; double* daction; int act_c; int gps;
 };
 
-template <int WM, int WN, int TM, int TN, bool VEC, int VM>
+// DET (deterministic mode): e.dbeta / e.dgamma are slot planes of e.stat_stride doubles per block (as in gemm_fwd_kernel)
+template <int WM, int WN, int TM, int TN, bool VEC, int VM, bool DET = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemm_dx_kernel(DzSrc d, Groups gr, const int32_t* __restrict__ n_rows_dev,
                                                        int n_rows_static, const float* __restrict__ W, int Kp,
                                                        DxEpi e, unsigned long long* __restrict__ ts) {
@@ -2103,10 +2252,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         __syncthreads();
     }
     if (e.dbeta) {
-        const int rep = blockIdx.x % GAD_STAT_REPLICAS;
-        block_column_atomics<WM, WN, TN>(smem, cb, cg, lane, wm, wn, k0out, e.k_valid,
-                                         e.dbeta + (size_t)rep * e.stat_stride + goff,
-                                         e.dgamma + (size_t)rep * e.stat_stride + goff);
+        const int rep = DET ? blockIdx.x : blockIdx.x % GAD_STAT_REPLICAS;
+        block_column_atomics<WM, WN, TN, DET>(smem, cb, cg, lane, wm, wn, k0out, e.k_valid,
+                                              e.dbeta + (size_t)rep * e.stat_stride + goff,
+                                              e.dgamma + (size_t)rep * e.stat_stride + goff);
     }
 }
 
@@ -3160,7 +3309,7 @@ __global__ __launch_bounds__(256) void dx_action_stream_kernel(DzSrc d, const in
 
 // the action-gradient layer: scatter epilogue that wants nothing but daction, G source, 64 channels, 6 action components
 static bool dx_action_streamable(const gad_gemm_dx_args& a, bool vec) {
-    if (!g_opt_dx_stream || !vec || a.n_groups != 1 || a.dz_off[0] != 0 || a.w_off[0] != 0) return false;
+    if (g_opt_deterministic || !g_opt_dx_stream || !vec || a.n_groups != 1 || a.dz_off[0] != 0 || a.w_off[0] != 0) return false;
     if (a.epilogue != 1 || a.dfeat || !a.daction || a.act_c != 6 || !a.row_grp || a.n_rows < 32768 || a.n_out[0] != 64) return false;
     const gad_dz_src& d = a.dz;
     return d.gmode == 0 && d.G && d.z && d.z_pitch % 4 == 0 && d.g_pitch % 4 == 0 && d.premasked && d.coefP && d.coefQ && d.coefS &&
@@ -3168,7 +3317,7 @@ static bool dx_action_streamable(const gad_gemm_dx_args& a, bool vec) {
 }
 
 static bool dx_wideable(const gad_gemm_dx_args& a, bool vec) {
-    if (!g_opt_dx_wide || !vec || a.n_groups != 1 || a.dz_off[0] != 0 || a.w_off[0] != 0 || a.gout_off[0] != 0) return false;
+    if (g_opt_deterministic || !g_opt_dx_wide || !vec || a.n_groups != 1 || a.dz_off[0] != 0 || a.w_off[0] != 0 || a.gout_off[0] != 0) return false;
     if (a.n_rows < 2048 || a.k_valid % 128 != 0 || a.k_valid > a.Kp) return false;
     if (a.n_out[0] % 32 != 0 || a.n_out[0] < 32 || a.n_out[0] > 512) return false;
     if (a.epilogue == 1) {                               // scatter into the points' feature gradients (SA2 / SA3 first layers)
@@ -3181,7 +3330,7 @@ static bool dx_wideable(const gad_gemm_dx_args& a, bool vec) {
 }
 
 static bool dx_streamable(const gad_gemm_dx_args& a, bool vec) {
-    if (!g_opt_dx_stream || !vec || a.n_groups != 1 || a.dz_off[0] != 0 || a.w_off[0] != 0 || a.gout_off[0] != 0) return false;
+    if (g_opt_deterministic || !g_opt_dx_stream || !vec || a.n_groups != 1 || a.dz_off[0] != 0 || a.w_off[0] != 0 || a.gout_off[0] != 0) return false;
     if (a.n_rows < 32768 || a.epilogue != 0 || a.k_valid != 64 || a.Kp != 64 || a.gout_pitch != 64) return false;
     if (a.n_out[0] != 64 && a.n_out[0] != 128) return false;
     if (!a.prev_dbeta || a.zprev_pitch != 64 || !a.store_masked) return false;
@@ -3369,6 +3518,165 @@ static int coef_fallback(gad_dz_src& dz, void* stream) {
     return GAD_OK;
 }
 
+// deterministic mode, gathered first layer.  rowbuf = the rows' input gradients [row][pitch] (feature columns, 3 coordinate
+// columns, action columns), as gemm_dx_kernel stored them; rows are ordered by group (include/gaddpg.h section B).
+__device__ __forceinline__ int rows_lower_bound(const int32_t* __restrict__ row_grp, int n, int key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (row_grp[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// Feature columns: the rows are cut into RUNS that share no point, found from the data alone (no reliance on grp_per_sample): a
+// cut goes before group g when every point the rows before it reference is below every point the rows from g on reference
+// (prefix max < suffix min).  One workgroup per run, thread = column, the run's rows walked in ascending order: each point's
+// contributions all lie in one run, so every dfeat element is written by one thread, in row order.  With the ball query's rows
+// (a sample's rows reference only its own points, samples' points ascending) a run is at most one sample.
+// (1) per-group point bounds: gmin / gmax (empty group: INT_MAX / -1); G > gcap marks the whole call as one run
+__global__ __launch_bounds__(256) void scatter_group_bounds_kernel(const int32_t* __restrict__ row_pt, const int32_t* __restrict__ row_grp,
+                                                                   const int32_t* __restrict__ n_rows_dev, int n_rows_static, int gcap,
+                                                                   int32_t* __restrict__ gmin, int32_t* __restrict__ gmax) {
+    const int n_rows = n_rows_dev ? min(*n_rows_dev, n_rows_static) : n_rows_static;
+    if (n_rows <= 0) return;
+    const int G = min(row_grp[n_rows - 1] + 1, gcap);
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= G) return;
+    const int r0 = rows_lower_bound(row_grp, n_rows, g), r1 = rows_lower_bound(row_grp, n_rows, g + 1);
+    int lo = INT_MAX, hi = -1;
+    for (int r = r0; r < r1; ++r) { const int p = row_pt[r]; lo = min(lo, p); hi = max(hi, p); }
+    gmin[g] = lo;
+    gmax[g] = hi;
+}
+// (2) one workgroup: head[g] = 1 where a run starts (prefix max of gmax before g < suffix min of gmin from g on)
+__global__ __launch_bounds__(256) void scatter_run_heads_kernel(const int32_t* __restrict__ row_grp, const int32_t* __restrict__ n_rows_dev,
+                                                                int n_rows_static, int gcap, const int32_t* __restrict__ gmin,
+                                                                const int32_t* __restrict__ gmax, int32_t* __restrict__ head) {
+    __shared__ int32_t lmax[256], lmin[256];
+    const int n_rows = n_rows_dev ? min(*n_rows_dev, n_rows_static) : n_rows_static;
+    if (n_rows <= 0) return;
+    const int Gall = row_grp[n_rows - 1] + 1;
+    const int G = min(Gall, gcap);
+    const int t = threadIdx.x, chunk = (G + 255) / 256;
+    const int g0 = min(G, t * chunk), g1 = min(G, g0 + chunk);
+    int mx = -1, mn = INT_MAX;
+    for (int g = g0; g < g1; ++g) { mx = max(mx, gmax[g]); mn = min(mn, gmin[g]); }
+    lmax[t] = mx; lmin[t] = mn;
+    __syncthreads();
+    if (t == 0) {                                        // exclusive prefix max / suffix min over the 256 chunks, in place
+        int run = -1;
+        for (int i = 0; i < 256; ++i) { const int v = lmax[i]; lmax[i] = run; run = max(run, v); }
+        run = INT_MAX;
+        for (int i = 255; i >= 0; --i) { const int v = lmin[i]; lmin[i] = run; run = min(run, v); }
+    }
+    __syncthreads();
+    int sm = lmin[t];
+    for (int g = g1 - 1; g >= g0; --g) { sm = min(sm, gmin[g]); head[g] = sm; }      // suffix min from g on
+    int pm = lmax[t];
+    for (int g = g0; g < g1; ++g) {
+        const int suf = head[g];
+        head[g] = (g == 0 || pm < suf) && Gall <= gcap ? 1 : 0;
+        pm = max(pm, gmax[g]);
+    }
+    if (Gall > gcap && t == 0) head[0] = 1;              // (more groups than the bounds arrays hold: one run)
+}
+// (3) the runs
+__global__ __launch_bounds__(256) void scatter_runs_kernel(const float* __restrict__ rowbuf, int pitch, const int32_t* __restrict__ row_pt,
+                                                           const int32_t* __restrict__ row_grp, const int32_t* __restrict__ n_rows_dev,
+                                                           int n_rows_static, int gcap, const int32_t* __restrict__ head, int feat_c,
+                                                           float* dfeat) {
+    const int n_rows = n_rows_dev ? min(*n_rows_dev, n_rows_static) : n_rows_static;
+    if (n_rows <= 0) return;
+    const int Gall = row_grp[n_rows - 1] + 1;
+    const int G = min(Gall, gcap);
+    for (int g = blockIdx.x; g < G; g += gridDim.x) {
+        if (!head[g]) continue;
+        int ge = g + 1;
+        while (ge < G && !head[ge]) ++ge;
+        const int r0 = rows_lower_bound(row_grp, n_rows, g);
+        const int r1 = ge < G ? rows_lower_bound(row_grp, n_rows, ge) : n_rows;
+        for (int c = threadIdx.x; c < feat_c; c += 256)
+            for (int r = r0; r < r1; ++r) {
+                float* p = dfeat + (size_t)row_pt[r] * feat_c + c;
+                *p = *p + rowbuf[(size_t)r * pitch + c];
+            }
+    }
+}
+
+// Action columns (per-sample sums: the sample of a row is row_grp / grp_per_sample, as in the default kernels): one workgroup per
+// sample, thread = column, the sample's rows summed in ascending order in f64 and added once into daction.
+__global__ __launch_bounds__(256) void gather_action_ordered_kernel(const float* __restrict__ rowbuf, int pitch,
+                                                                    const int32_t* __restrict__ row_grp, const int32_t* __restrict__ n_rows_dev,
+                                                                    int n_rows_static, int gps, int act_off, int act_c, double* daction) {
+    const int n_rows = n_rows_dev ? min(*n_rows_dev, n_rows_static) : n_rows_static;
+    if (n_rows <= 0) return;
+    const int n_smp = row_grp[n_rows - 1] / gps + 1;
+    for (int s = blockIdx.x; s < n_smp; s += gridDim.x) {
+        const int r0 = rows_lower_bound(row_grp, n_rows, s * gps), r1 = rows_lower_bound(row_grp, n_rows, (s + 1) * gps);
+        for (int j = threadIdx.x; j < act_c; j += 256) {
+            double acc = 0.0;
+            for (int r = r0; r < r1; ++r) acc += (double)rowbuf[(size_t)r * pitch + act_off + j];
+            daction[(size_t)s * act_c + j] += acc;
+        }
+    }
+}
+
+// the 64 x 64 tile dX launch of the deterministic mode: statistics through slots + ordered reduce; the gathered first layer's scatter
+// as row-buffer stores (the same kernel's plain-store epilogue) + the ordered scatter kernels above
+template <int WM, int WN, int TM, int TN, bool V>
+static int det_dx_launch(const gad_gemm_dx_args* a, const DzSrc& d, Groups gr, DxEpi e, int gx, int nmax_dx, unsigned long long* ts,
+                         void* stream) {
+    constexpr int BN = WN * TN * 32;
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = a->n_rows, kv = a->k_valid;
+    const dim3 grid(gx, gad_cdiv(kv, BN), gr.n);
+    double* slots = nullptr;
+    int ncol = 0;
+    if (e.mode == 1) {
+        GAD_REQUIRE(gr.n == 1 && !e.dbeta, GAD_ERR_UNSUPPORTED, "gemm_dx: the deterministic scatter epilogue takes one group and no "
+                    "previous-layer statistics");
+        GAD_REQUIRE(kv >= (a->daction && a->act_c > 0 ? a->feat_c + 3 + a->act_c : a->feat_c), GAD_ERR_SHAPE,
+                    "gemm_dx: k_valid=%d does not cover the scattered columns", kv);
+        float* rowbuf = static_cast<float*>(gad_det_scratch(stream, GAD_DET_ROWS, (size_t)rows * kv * sizeof(float)));
+        if (!rowbuf) return GAD_ERR_LAUNCH;
+        e.mode = 0; e.gout = rowbuf; e.gout_pitch = kv; e.store_masked = 0;
+        gr.ooff[0] = 0;
+    } else if (e.dbeta) {
+        for (int i = 0; i < gr.n; ++i) ncol = gr.ooff[i] + kv > ncol ? gr.ooff[i] + kv : ncol;
+        slots = det_stat_slots(gx, ncol, stream);
+        if (!slots) return GAD_ERR_LAUNCH;
+        e.dbeta = slots; e.dgamma = slots + (size_t)gx * ncol; e.stat_stride = ncol;
+    }
+    if (slots) {
+        if (nmax_dx <= 512) hipLaunchKernelGGL((gemm_dx_kernel<WM, WN, TM, TN, V, 512, true>), grid, dim3(256), 0, st, d, gr, a->n_rows_dev, rows, a->W, a->Kp, e, ts);
+        else                hipLaunchKernelGGL((gemm_dx_kernel<WM, WN, TM, TN, V, VMAX, true>), grid, dim3(256), 0, st, d, gr, a->n_rows_dev, rows, a->W, a->Kp, e, ts);
+    } else {
+        if (nmax_dx <= 512) hipLaunchKernelGGL((gemm_dx_kernel<WM, WN, TM, TN, V, 512>), grid, dim3(256), 0, st, d, gr, a->n_rows_dev, rows, a->W, a->Kp, e, ts);
+        else                hipLaunchKernelGGL((gemm_dx_kernel<WM, WN, TM, TN, V, VMAX>), grid, dim3(256), 0, st, d, gr, a->n_rows_dev, rows, a->W, a->Kp, e, ts);
+    }
+    GAD_CHECK_LAUNCH("gemm_dx");
+    if (slots) return det_stat_reduce(slots, gx, ncol, a->prev_dbeta, a->prev_dgamma, stream);
+    if (a->epilogue == 1 && a->dfeat) {
+        const int gcap = rows;                           // (a group has at least one row: at most `rows` groups)
+        int32_t* b = static_cast<int32_t*>(gad_det_scratch(stream, GAD_DET_RUNS, 3 * (size_t)gcap * sizeof(int32_t)));
+        if (!b) return GAD_ERR_LAUNCH;
+        int32_t *gmin = b, *gmax = b + gcap, *head = b + 2 * (size_t)gcap;
+        hipLaunchKernelGGL(scatter_group_bounds_kernel, dim3(gad_cdiv(gcap, 256)), dim3(256), 0, st, a->row_pt, a->row_grp, a->n_rows_dev,
+                           rows, gcap, gmin, gmax);
+        hipLaunchKernelGGL(scatter_run_heads_kernel, dim3(1), dim3(256), 0, st, a->row_grp, a->n_rows_dev, rows, gcap, gmin, gmax, head);
+        hipLaunchKernelGGL(scatter_runs_kernel, dim3(1024), dim3(256), 0, st, e.gout, kv, a->row_pt, a->row_grp, a->n_rows_dev, rows, gcap,
+                           head, a->feat_c, a->dfeat);
+        GAD_CHECK_LAUNCH("scatter_runs");
+    }
+    if (a->epilogue == 1 && a->daction && a->act_c > 0) {
+        hipLaunchKernelGGL(gather_action_ordered_kernel, dim3(1024), dim3(256), 0, st, e.gout, kv, a->row_grp, a->n_rows_dev, rows, e.gps,
+                           a->feat_c + 3, a->act_c, a->daction);
+        GAD_CHECK_LAUNCH("gather_action_ordered");
+    }
+    return GAD_OK;
+}
+
 extern "C" int gad_gemm_dx(const gad_gemm_dx_args* a, void* stream) {
     unsigned long long* ts = gad_take_timing_slot(stream);
     const int rows_hint = gad_take_grid_rows();
@@ -3442,7 +3750,7 @@ extern "C" int gad_gemm_dx(const gad_gemm_dx_args* a, void* stream) {
     }
     int nmax_dx = 0;
     for (int i = 0; i < a->n_groups; ++i) nmax_dx = a->n_out[i] > nmax_dx ? a->n_out[i] : nmax_dx;
-    if (g_opt_dx_skinny && vec && e.mode == 0 && a->dz.gmode == 0 && !a->n_rows_dev && rows <= 1024 &&
+    if (!g_opt_deterministic && g_opt_dx_skinny && vec && e.mode == 0 && a->dz.gmode == 0 && !a->n_rows_dev && rows <= 1024 &&
         nmax_dx <= VMAX) {
         if (g_opt_skinny_nw == 4)
             hipLaunchKernelGGL(gemm_dx_skinny_kernel<4>, dim3(gad_cdiv(kv, 32), gad_cdiv(rows, 32), gr.n), dim3(64 * 4), 0, st, d, gr,
@@ -3457,6 +3765,10 @@ extern "C" int gad_gemm_dx(const gad_gemm_dx_args* a, void* stream) {
     do {                                                                                                 \
         constexpr int BM = WM * TM * 32, BN = WN * TN * 32;                                              \
         int gx = gad_cdiv(grid_rows, BM); if (gx > GAD_GX_CAP) gx = GAD_GX_CAP;                                      \
+        if (g_opt_deterministic) {                                                                       \
+            if (int e_ = det_dx_launch<WM, WN, TM, TN, V>(a, d, gr, e, gx, nmax_dx, ts, stream)) return e_; \
+            return GAD_OK;                                                                               \
+        }                                                                                                \
         if (nmax_dx <= 512)                                                                              \
             hipLaunchKernelGGL((gemm_dx_kernel<WM, WN, TM, TN, V, 512>), dim3(gx, gad_cdiv(kv, BN), gr.n), dim3(256), 0, \
                                st, d, gr, a->n_rows_dev, rows, a->W, a->Kp, e, ts);                          \
@@ -4423,7 +4735,7 @@ __global__ __launch_bounds__(256, 1) void gemm_dw_wide_split_kernel(DzSrc d, XSr
 static bool dw_wideable(const gad_gemm_dw_args& a, int k_used, bool vec) {
     const gad_gemm_fwd_args& in = a.in;
     const gad_dz_src& d = a.dz;
-    if (!g_opt_dw_wide || !vec || in.n_groups != 1 || in.zin_off[0] != 0 || a.dz_off[0] != 0) return false;
+    if (g_opt_deterministic || !g_opt_dw_wide || !vec || in.n_groups != 1 || in.zin_off[0] != 0 || a.dz_off[0] != 0) return false;
     if (in.n_rows < 2048 || in.n_out[0] % 128 != 0 || in.n_out[0] > 512 || in.ones_col >= 0) return false;
     if (in.mode == 1) {                                  // gathered first layer: features a multiple of 128, + 3 coordinates
         if (g_opt_dw_wide == 2 || d.gmode != 0 || in.act_c != 0 || in.feat_c % 128 != 0 || in.feat_c > 512) return false;
@@ -4440,7 +4752,7 @@ static bool dw_wideable(const gad_gemm_dw_args& a, int k_used, bool vec) {
 static bool dw_gather_streamable(const gad_gemm_dw_args& a, int k_used) {
     const gad_gemm_fwd_args& in = a.in;
     const gad_dz_src& d = a.dz;
-    if (!g_opt_dw_stream || in.mode != 1 || in.n_groups != 1 || in.Kp > 32 || in.n_out[0] != 64 || k_used > in.Kp) return false;
+    if (g_opt_deterministic || !g_opt_dw_stream || in.mode != 1 || in.n_groups != 1 || in.Kp > 32 || in.n_out[0] != 64 || k_used > in.Kp) return false;
     if (in.zin_off[0] != 0 || a.dz_off[0] != 0 || in.n_rows < 32768 || d.gmode != 0 || !d.G) return false;
     if (!d.z || !d.scale || !d.relu || !d.premasked || !(d.coefP && d.coefQ && d.coefS)) return false;
     if (in.feat_c + 3 + (in.action ? in.act_c : 0) > in.Kp) return false;
@@ -4451,13 +4763,23 @@ static bool dw_gather_streamable(const gad_gemm_dw_args& a, int k_used) {
 static bool dw_streamable(const gad_gemm_dw_args& a, int k_used) {
     const gad_gemm_fwd_args& in = a.in;
     const gad_dz_src& d = a.dz;
-    if (!g_opt_dw_stream || in.mode != 0 || in.n_groups != 1 || in.Kp != 64 || in.c_in != 64 || k_used != 64) return false;
+    if (g_opt_deterministic || !g_opt_dw_stream || in.mode != 0 || in.n_groups != 1 || in.Kp != 64 || in.c_in != 64 || k_used != 64) return false;
     if (in.zin_off[0] != 0 || a.dz_off[0] != 0 || (in.n_out[0] != 64 && in.n_out[0] != 128)) return false;   // w_off: arena offset, dw_reduce applies it
     if (in.n_rows < 32768 || !in.scale || !in.shift || !in.relu || in.extra || in.ones_col >= 0) return false;
     if (!d.z || !d.scale || !d.relu || !d.premasked || !(d.coefP && d.coefQ && d.coefS)) return false;
     if (d.gmode != 0 && d.c != in.n_out[0]) return false;
     if (!a.partial || (long long)DW_STREAM_SPLITS * in.n_out[0] * 64 > a.partial_elems) return false;
     return a.row_splits <= 0;
+}
+
+// deterministic mode: the zeroed partial-dW slab of a split generic dW launch (splits past the live rows write nothing: zeros)
+static float* det_dw_slab(long long elems, void* stream) {
+    float* p = static_cast<float*>(gad_det_scratch(stream, GAD_DET_SLOTS2, (size_t)elems * sizeof(float)));
+    if (p && hipMemsetAsync(p, 0, (size_t)elems * sizeof(float), (hipStream_t)stream) != hipSuccess) {
+        gad_set_error("deterministic mode: clearing the partial dW slab failed");
+        return nullptr;
+    }
+    return p;
 }
 
 extern "C" int gad_gemm_dw(const gad_gemm_dw_args* a, void* stream) {
@@ -4481,7 +4803,7 @@ extern "C" int gad_gemm_dw(const gad_gemm_dw_args* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const int rows = in.n_rows;
     const bool vec = dz_vectorizable(a->dz, a->dz_off, in.n_out, in.n_groups);
-    const bool skinny_route = g_opt_dw_skinny && in.mode == 0 && a->dz.gmode == 0 && !in.n_rows_dev && rows <= 1024;
+    const bool skinny_route = !g_opt_deterministic && g_opt_dw_skinny && in.mode == 0 && a->dz.gmode == 0 && !in.n_rows_dev && rows <= 1024;
     if (a->dz.bn_dbeta && (skinny_route || dw_gather_streamable(*a, k_used) || dw_streamable(*a, k_used))) {
         gad_dz_src dz2 = a->dz;                          // these kernels read P / Q / S per lane: gad_bn_bwd_coef first
         if (int e2 = coef_fallback(dz2, stream)) return e2;
@@ -4579,6 +4901,10 @@ extern "C" int gad_gemm_dw(const gad_gemm_dw_args* a, void* stream) {
         }                                                                                                  \
         group_stride = (long long)splits * nmax * in.Kp;                                                   \
         if (part && (splits == 1 || group_stride * gr.n > a->partial_elems)) part = nullptr; \
+        if (g_opt_deterministic) {               /* every split's partial into the mode's zeroed slab, summed in order */ \
+            part = splits > 1 ? det_dw_slab(group_stride * gr.n, stream) : nullptr;                       \
+            if (splits > 1 && !part) return GAD_ERR_LAUNCH;                                                \
+        }                                                                                                  \
         if (in.mode == 0) { if (vec) LAUNCH_DW3(WM, WN, TM, TN, 0, true); else LAUNCH_DW3(WM, WN, TM, TN, 0, false); } \
         else              { if (vec) LAUNCH_DW3(WM, WN, TM, TN, 1, true); else LAUNCH_DW3(WM, WN, TM, TN, 1, false); } \
     } while (0)
@@ -4596,7 +4922,11 @@ extern "C" int gad_gemm_dw(const gad_gemm_dw_args* a, void* stream) {
 #undef LAUNCH_DW3
 #undef LAUNCH_DW4
     GAD_CHECK_LAUNCH("gemm_dw");
-    if (part) {
+    if (part && g_opt_deterministic) {
+        for (int g = 0; g < gr.n; ++g)
+            if (int e = gad_ordered_reduce(part + (size_t)g * group_stride, (long long)gr.nout[g] * in.Kp, splits,
+                                           (long long)gr.nout[g] * in.Kp, a->gacc + gr.woff[g], stream)) return e;
+    } else if (part) {
         hipLaunchKernelGGL(dw_reduce_kernel, dim3(gad_cdiv((long long)nmax * in.Kp, 256), gad_cdiv(splits, DW_RED_CHUNK), gr.n),
                            dim3(256), 0, st, part,
                            group_stride, gr, in.n_rows_dev, rows, splits, in.Kp, k_used, a->gacc);
@@ -4903,7 +5233,7 @@ static int bwd_wide_splits(const gad_gemm_dx_args& ax) {
 // sides (premasked gradients), N in {128, 256, 512}, K a multiple of 64; the gathered first layers with their scatter epilogue
 static bool bwd_wideable(const gad_gemm_dx_args& ax, const gad_gemm_dw_args& aw, bool vec) {
     const gad_gemm_fwd_args& in = aw.in;
-    if (!g_opt_bwd_wide || !vec || ax.n_groups != 1 || in.n_groups != 1) return false;
+    if (g_opt_deterministic || !g_opt_bwd_wide || !vec || ax.n_groups != 1 || in.n_groups != 1) return false;
     if (ax.dz_off[0] != 0 || ax.w_off[0] != 0 || ax.gout_off[0] != 0 || in.zin_off[0] != 0 || aw.dz_off[0] != 0) return false;
     const int N = ax.n_out[0];
     if (N != 128 && N != 256 && N != 512) return false;
@@ -4929,7 +5259,7 @@ static bool bwd_wideable(const gad_gemm_dx_args& ax, const gad_gemm_dw_args& aw,
 
 static bool bwd_streamable(const gad_gemm_dx_args* ax, const gad_gemm_dw_args* aw) {
     const gad_gemm_fwd_args& in = aw->in;
-    if (!g_opt_bwd_fused) return false;
+    if (g_opt_deterministic || !g_opt_bwd_fused) return false;
     const bool vec = dz_vectorizable(ax->dz, ax->dz_off, ax->n_out, ax->n_groups);
     int k_used = in.mode == 0 ? in.c_in + (in.extra ? 1 : 0) : in.feat_c + 3 + in.act_c;
     bool fused = dx_streamable(*ax, vec) && dw_streamable(*aw, k_used);

@@ -53,7 +53,7 @@ static thread_local int g_grid_rows = 0;
 int gad_take_grid_rows() {
     const int r = g_grid_rows;
     g_grid_rows = 0;
-    return r;
+    return gad_deterministic() ? 0 : r;          // the mode sizes every grid by the row capacity: hints cannot regroup partial sums
 }
 extern "C" int gad_grid_rows_hint(const int32_t* rows_host, void* /*stream: unused, plan calls pass one*/) {
     g_grid_rows = rows_host ? *rows_host : 0;
@@ -1077,10 +1077,49 @@ __global__ __launch_bounds__(256) void group_points_grad_kernel(const float* __r
     atomic_add_f32(gp + (size_t)bc * N + idx[(size_t)b * MS + ms], go[q]);
 }
 
+// deterministic mode: one workgroup per (sample, channel) row of grad_points; thread t owns the points n = t (mod 256) of an LDS tile
+// of GPG_NT points and applies the (m, s) entries that land on them in ascending order (entries staged 256 at a time).  Every
+// destination is written by one thread, in entry order: the result does not depend on scheduling.  N > GPG_NT: one pass per tile.
+#define GPG_NT 8192
+__global__ __launch_bounds__(256) void group_points_grad_ordered_kernel(const float* __restrict__ go, const int32_t* __restrict__ idx,
+                                                                        int C, int N, int MS, float* __restrict__ gp) {
+    __shared__ float acc[GPG_NT];
+    __shared__ int32_t iS[256];
+    __shared__ float vS[256];
+    const int bc = blockIdx.x, b = bc / C, t = threadIdx.x;
+    const float* gor = go + (size_t)bc * MS;
+    const int32_t* ir = idx + (size_t)b * MS;
+    for (int n0 = 0; n0 < N; n0 += GPG_NT) {
+        const int nt = min(GPG_NT, N - n0);
+        for (int i = t; i < nt; i += 256) acc[i] = 0.f;
+        for (int q0 = 0; q0 < MS; q0 += 256) {
+            __syncthreads();                             // acc cleared / the previous chunk consumed
+            const int q = q0 + t;
+            iS[t] = q < MS ? ir[q] - n0 : -1;
+            vS[t] = q < MS ? gor[q] : 0.f;
+            __syncthreads();
+            const int nq = min(256, MS - q0);
+            for (int j = 0; j < nq; ++j) {
+                const int n = iS[j];
+                if (n >= 0 && n < nt && (n & 255) == t) acc[n] += vS[j];
+            }
+        }
+        __syncthreads();
+        for (int i = t; i < nt; i += 256) gp[(size_t)bc * N + n0 + i] = acc[i];
+    }
+}
+
 extern "C" int gad_group_points_grad(const float* grad_out, const int32_t* idx, int B, int C, int N, int M,
                                      int S, float* grad_points, void* stream) {
     GAD_REQUIRE(grad_out && idx && grad_points, GAD_ERR_NULL, "group_points_grad: null pointer");
     hipStream_t st = (hipStream_t)stream;
+    if (gad_deterministic()) {                           // (writes every element of grad_points: no clearing pass)
+        if ((long long)B * C * N == 0) return GAD_OK;
+        GAD_REQUIRE((long long)B * C < (1ll << 31), GAD_ERR_SHAPE, "group_points_grad: B * C too large");
+        hipLaunchKernelGGL(group_points_grad_ordered_kernel, dim3(B * C), dim3(256), 0, st, grad_out, idx, C, N, M * S, grad_points);
+        GAD_CHECK_LAUNCH("group_points_grad");
+        return GAD_OK;
+    }
     if ((long long)B * C * N > 0) { hipError_t me = hipMemsetAsync(grad_points, 0, sizeof(float) * (size_t)B * C * N, st); (void)me; }
     const long long total = (long long)B * C * M * S;
     if (total == 0) return GAD_OK;

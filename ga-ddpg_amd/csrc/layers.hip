@@ -335,6 +335,9 @@ extern "C" int gad_transpose_batched(const float* src, float* dst, int B, int R,
 }
 
 // dbeta[c] += sum_g dout[g][c]*[y*>0],  dgamma[c] += sum_g dout[g][c]*[y*>0]*xhat*  (* = arg-max row)
+// DET (deterministic mode): dbeta / dgamma are slot planes, slot = blockIdx.y * (256 / cpb) + the thread's group lane, `stride`
+// doubles apart; every slot of every channel is stored (no atomics), gad_ordered_reduce sums them in slot order
+template <bool DET = false>
 __global__ __launch_bounds__(256) void pool_bwd_stats_kernel(float* __restrict__ dout,
                                                              const int32_t* __restrict__ argmax, int G, int C,
                                                              const float* __restrict__ z, int z_pitch,
@@ -375,6 +378,12 @@ __global__ __launch_bounds__(256) void pool_bwd_stats_kernel(float* __restrict__
             else if (mask) dout[(size_t)g * C + c] = 0.f;
         }
     }
+    if (DET) {
+        const size_t slot = (size_t)blockIdx.y * gl + threadIdx.x / cpb;
+        dbeta[slot * stride + c] = (double)sb;
+        dgamma[slot * stride + c] = (double)sg;
+        return;
+    }
     const int rep = blockIdx.y % GAD_STAT_REPLICAS;
     atomic_add_f64(dbeta + (size_t)rep * stride + c, (double)sb);
     atomic_add_f64(dgamma + (size_t)rep * stride + c, (double)sg);
@@ -392,6 +401,16 @@ extern "C" int gad_pool_bwd_stats(float* dout, const int32_t* argmax, int G, int
     int gy = gad_cdiv(G, gl * 4);
     if (gy > 512) gy = 512;                       // (1024 / 2048 workgroups: -0.5 / -1 % steps/s -- more same-address atomics)
     if (gy < 1) gy = 1;
+    if (gad_deterministic()) {                    // (the grid depends on G and C only: the slots are the same for every run)
+        const int nslots = gy * gl;
+        double* slots = static_cast<double*>(gad_det_scratch(stream, GAD_DET_SLOTS, 2 * (size_t)nslots * C * sizeof(double)));
+        if (!slots) return GAD_ERR_LAUNCH;
+        hipLaunchKernelGGL(pool_bwd_stats_kernel<true>, dim3(C / cpb, gy), dim3(256), 0, (hipStream_t)stream, dout, argmax, G, C,
+                           z, z_pitch, scale, shift, mean, istd, slots, slots + (size_t)nslots * C, C, mask_in_place, zmax);
+        GAD_CHECK_LAUNCH("pool_bwd_stats");
+        if (int e = gad_ordered_reduce(slots, C, nslots, C, dbeta, stream)) return e;
+        return gad_ordered_reduce(slots + (size_t)nslots * C, C, nslots, C, dgamma, stream);
+    }
     hipLaunchKernelGGL(pool_bwd_stats_kernel, dim3(C / cpb, gy), dim3(256), 0, (hipStream_t)stream, dout, argmax, G, C,
                        z, z_pitch, scale, shift, mean, istd, dbeta, dgamma, stat_stride, mask_in_place, zmax);
     GAD_CHECK_LAUNCH("pool_bwd_stats");

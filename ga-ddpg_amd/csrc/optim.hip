@@ -18,6 +18,8 @@ __global__ __launch_bounds__(256) void grad_from_arena_kernel(const double* __re
 
 // the same conversion + the sum of squares of the resulting gradient (clip_grad_norm_'s total norm): one launch fewer on the
 // critic phase's chain than gad_grad_from_arena followed by gad_sumsq
+// DET (deterministic mode): `out` is a slot array, block b stores its partial in out[b] (summed in order by gad_ordered_reduce)
+template <bool DET = false>
 __global__ __launch_bounds__(256) void grad_from_arena_sumsq_kernel(const double* __restrict__ gacc, const int32_t* __restrict__ m2p, int n,
                                                                     float* __restrict__ grad, int accumulate, double* __restrict__ out) {
     __shared__ double red[4];
@@ -32,7 +34,15 @@ __global__ __launch_bounds__(256) void grad_from_arena_sumsq_kernel(const double
     s = wave_sum_d(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) atomic_add_f64(out, red[0] + red[1] + red[2] + red[3]);
+    if (threadIdx.x == 0) {
+        if (DET) out[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+        else atomic_add_f64(out, red[0] + red[1] + red[2] + red[3]);
+    }
+}
+
+// deterministic mode: per-block partials of a sum of squares -> slots -> ordered sum into *out
+static double* det_sumsq_slots(int gx, void* stream) {
+    return static_cast<double*>(gad_det_scratch(stream, GAD_DET_SLOTS, (size_t)gx * sizeof(double)));
 }
 
 extern "C" int gad_grad_from_arena_sumsq(const double* gacc, const int32_t* m2p, int n, float* grad, int accumulate, double* sumsq,
@@ -41,6 +51,13 @@ extern "C" int gad_grad_from_arena_sumsq(const double* gacc, const int32_t* m2p,
     if (n <= 0) return GAD_OK;
     int gx = gad_cdiv(n, 1024);
     gx = gx < 1 ? 1 : gx;
+    if (gad_deterministic()) {
+        double* slots = det_sumsq_slots(gx, stream);
+        if (!slots) return GAD_ERR_LAUNCH;
+        hipLaunchKernelGGL(grad_from_arena_sumsq_kernel<true>, dim3(gx), dim3(256), 0, (hipStream_t)stream, gacc, m2p, n, grad, accumulate, slots);
+        GAD_CHECK_LAUNCH("grad_from_arena_sumsq");
+        return gad_ordered_reduce(slots, 1, gx, 1, sumsq, stream);
+    }
     hipLaunchKernelGGL(grad_from_arena_sumsq_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, gacc, m2p, n, grad, accumulate, sumsq);
     GAD_CHECK_LAUNCH("grad_from_arena_sumsq");
     return GAD_OK;
@@ -56,6 +73,7 @@ extern "C" int gad_grad_from_arena(const double* gacc, const int32_t* m2p, int n
     return GAD_OK;
 }
 
+template <bool DET = false>   // DET: as grad_from_arena_sumsq_kernel
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, int n, double* __restrict__ out) {
     __shared__ double red[4];
     double s = 0.0;
@@ -63,7 +81,10 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
     s = wave_sum_d(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) atomic_add_f64(out, red[0] + red[1] + red[2] + red[3]);
+    if (threadIdx.x == 0) {
+        if (DET) out[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+        else atomic_add_f64(out, red[0] + red[1] + red[2] + red[3]);
+    }
 }
 
 extern "C" int gad_sumsq(const float* grad, int n, double* out, void* stream) {
@@ -71,6 +92,13 @@ extern "C" int gad_sumsq(const float* grad, int n, double* out, void* stream) {
     if (n <= 0) return GAD_OK;
     int gx = gad_cdiv(n, 256 * 8);
     if (gx > 512) gx = 512;
+    if (gad_deterministic()) {
+        double* slots = det_sumsq_slots(gx, stream);
+        if (!slots) return GAD_ERR_LAUNCH;
+        hipLaunchKernelGGL(sumsq_kernel<true>, dim3(gx), dim3(256), 0, (hipStream_t)stream, grad, n, slots);
+        GAD_CHECK_LAUNCH("sumsq");
+        return gad_ordered_reduce(slots, 1, gx, 1, out, stream);
+    }
     hipLaunchKernelGGL(sumsq_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, grad, n, out);
     GAD_CHECK_LAUNCH("sumsq");
     return GAD_OK;

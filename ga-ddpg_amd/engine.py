@@ -487,6 +487,12 @@ _SIDE = {}
 SERIAL = False            # bench.py / diagnostics: run the whole step on ONE stream (per-kernel durations without contention)
 
 
+def serial():
+    """one stream for everything: engine.SERIAL, or the deterministic mode (hip.deterministic()) -- there every launch that adds into
+    a shared accumulator (gradient arenas, statistics, running buffers) then runs in one fixed program order"""
+    return SERIAL or hip._lib_det[0] == 1
+
+
 # Logical stream -> physical HIP stream.  MEASURED (MI355X, ROCm 7.2, tools/bisect_bench.sh): ROCm runs the streams of a
 # process on GPU_MAX_HW_QUEUES = 4 hardware queues; a fifth active queue (GPU_MAX_HW_QUEUES >= 5, or one stream created with a
 # priority) drops the step rate from ~265 to ~140 steps/s, and streams beyond the fourth silently SHARE a queue with an earlier
@@ -534,7 +540,7 @@ def side_stream(device=None, which=0):
     3 = small initialisations, 10 + lane = weight-gradient GEMMs forked off a dX chain, 20 / 21 = input / geometry prefetch;
     several logical streams share a physical one (_PHYS)"""
     dev = torch.cuda.current_device() if device is None else torch.device(device).index
-    if SERIAL:                                   # diagnostics: every fork / join degenerates to the caller's stream
+    if serial():                                 # diagnostics / deterministic mode: every fork / join degenerates to the caller's stream
         return torch.cuda.current_stream(dev)
     key = (dev, _PHYS.get(which, which))
     if key not in _SIDE:
@@ -555,7 +561,7 @@ _PRIO_DONE = set()
 
 def apply_lane_priorities(main):
     """once per caller's stream: hand the GAD_LANE_PRIO table to the library"""
-    if not LANE_PRIO or SERIAL:
+    if not LANE_PRIO or serial():
         return
     dev = main.device.index
     key = (dev, int(main.cuda_stream))
@@ -700,7 +706,7 @@ class _Compiled(object):
     def table(self, main_handle):
         """lane -> hipStream_t table for a run whose current stream is main_handle"""
         import ctypes as C
-        key = (int(main_handle or 0), SERIAL)
+        key = (int(main_handle or 0), serial())
         t = self._tables.get(key)
         if t is None:
             hs = [int(main_handle or 0)] + [int(side_stream(which=w).cuda_stream) for w in self.whichs[1:]]
@@ -855,6 +861,7 @@ class Plan(object):
 
     # ---- replay -------------------------------------------------------------------------------------------------------
     def run(self):
+        hip.sync_deterministic()           # (torch.use_deterministic_algorithms may have changed since the last call)
         timed = TIMING["enabled"]
         if not USE_C_PLANS or (timed and any(it.tag is not None and it.name in _TIMED_CALLS and it.tag not in _ROUTES
                                               for it in self.calls)):
@@ -1331,8 +1338,9 @@ def plan_encoder_backward(enc, slot, g_fc2, action=None, want_dw=True, want_dact
             fc = slot.F[s - 1].shape[1]
             if zero_scatter:
                 plan.zero(slot.dF[s - 1])
+            # (groups per sample: the deterministic mode's scatter walks each sample's rows; the default kernels do not read it here)
             dx(dict(rows_kw, layer=1), d, m1, fc, epilogue=1, dfeat=_ptr(slot.dF[s - 1]), feat_c=fc, row_pt=_ptr(r["pt"]),
-               row_grp=_ptr(r["grp"]), act_c=0, grp_per_sample=1)
+               row_grp=_ptr(r["grp"]), act_c=0, grp_per_sample=geo.M2 if s == 1 else 1)
         elif has_dx:
             if zero_scatter:
                 plan.zero(slot.daction)

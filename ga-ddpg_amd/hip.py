@@ -113,6 +113,8 @@ def lib():
         for k, v in os.environ.items():          # GAD_OPT_<name>=<int>: kernel-selection switches for A/B diagnostics
             if k.startswith("GAD_OPT_"):
                 check(L.gad_set_option(k[8:].encode(), int(v)), "gad_set_option(%s)" % k[8:])
+        _lib_det[0] = get_option_default("deterministic")
+        sync_deterministic()
     return _lib
 
 
@@ -184,11 +186,13 @@ def call(name, *a):
     """Call an entry point: tensors -> device pointers, ints -> int, floats -> float, Dbl -> double,
     None -> NULL; the current torch stream is appended as the trailing `stream` argument."""
     f = getattr(lib(), name)
+    sync_deterministic()
     check(f(*(_args(*a) + [stream()])), name)
 
 
 def call_struct(name, s):
     f = getattr(lib(), name)
+    sync_deterministic()
     check(f(C.byref(s), stream()), name)
 
 
@@ -202,7 +206,7 @@ def require_cuda(*tensors):
 
 # options this package sets when it loads the library (the library's own default of "mfma_split" is 0 = the f32 MFMA: a plain C
 # caller opts in itself); also what a test restores
-OPTION_DEFAULTS = {"mfma_split": 1}
+OPTION_DEFAULTS = {"mfma_split": 1, "deterministic": 0}
 
 
 def get_option_default(name):
@@ -218,9 +222,38 @@ def set_option(name, value):
     """kernel-selection switch for A/B diagnostics (include/gaddpg.h: gad_set_option)"""
     check(lib().gad_set_option(name.encode(), int(value)), "gad_set_option")
     _options[name] = int(value)
+    if name == "deterministic":
+        _lib_det[0] = int(value)
+        sync_deterministic()
     ROUTES.clear()
 
 
 def get_option(name):
-    """the value last set through set_option (else the default / environment override)"""
+    """the value last set through set_option (else the default / environment override); "deterministic" reads 1 while
+    torch.use_deterministic_algorithms(True) is in force"""
+    if name == "deterministic":
+        return deterministic()
     return _options.get(name, get_option_default(name))
+
+
+# --- deterministic mode (library option "deterministic", include/gaddpg.h gad_set_option) ---
+# On when asked for through set_option / GAD_OPT_deterministic=1, and while torch's own switch for reproducible results,
+# torch.use_deterministic_algorithms(True), is in force: every entry point then gives bit-identical results run to run.
+_lib_det = [0]            # the value the library holds now
+
+
+def deterministic():
+    """1 if the deterministic mode is in force (requested, or torch.are_deterministic_algorithms_enabled())"""
+    if torch.are_deterministic_algorithms_enabled():
+        return 1
+    return int(bool(_options.get("deterministic", get_option_default("deterministic"))))
+
+
+def sync_deterministic():
+    """bring the library's "deterministic" option in line with deterministic(); a change invalidates the recorded routes"""
+    want = deterministic()
+    if want != _lib_det[0]:
+        check(lib().gad_set_option(b"deterministic", want), "gad_set_option(deterministic)")
+        _lib_det[0] = want
+        ROUTES.clear()
+    return want

@@ -587,7 +587,7 @@ class FusedRuntime(object):
         self._optim_jobs()
         return (self._jobs_gen, self._plans_gen, id(self.dp), id(self.allreduce), None if self.inv_n is None else self.inv_n.data_ptr(),
                 bool(ag.train_feature), float(ag.gamma), bool(ag.critic_aux), bool(ag.policy_aux), float(ag.clip_grad),
-                self.bucketed, ROW_HINTS, EARLY_ZERO)
+                self.bucketed, ROW_HINTS, EARLY_ZERO, hip.sync_deterministic())
 
     def _step_plan(self, set_index, policy_step):
         """The whole update step over input / geometry set `set_index` as one engine.Plan (what _ddpg_enqueue issues call by
@@ -762,7 +762,7 @@ class FusedRuntime(object):
         (sample, update, read the losses, every iteration: core/train_test_offline.py:117-126) keep the GPU busy across its
         host synchronisation: core.train_test_offline.train_off_policy samples one minibatch ahead and calls this.
         Device-resident minibatches only (DeviceReplay.sample_lazy, CUDA tensors); -> False when nothing was staged."""
-        if not (STEP_PLAN and OVERLAP_PASSES and self.fused_optim and self.has_critic) or engine.SERIAL or batch is None:
+        if not (STEP_PLAN and OVERLAP_PASSES and self.fused_optim and self.has_critic) or engine.serial() or batch is None:
             return False
         dev_batch = "replay_gather" in batch or (torch.is_tensor(batch.get("point_state_batch")) and batch["point_state_batch"].is_cuda)
         if not dev_batch or len(self._sets) < 2:
@@ -845,7 +845,7 @@ class FusedRuntime(object):
         # uploads + geometry of both cloud sets on the prefetch stream, into this step's input / geometry set: ordered only
         # after the last step that used the set, i.e. they run beside the previous step when the host is ahead of the GPU
         st = self._sets[self._set]
-        inline = (not OVERLAP_PASSES) or engine.SERIAL
+        inline = (not OVERLAP_PASSES) or engine.serial()
         spre = main if inline else engine.side_stream(which=20)
         spre2 = main if inline else engine.side_stream(which=21)
         if not inline:

@@ -248,7 +248,7 @@ class _StageRun(object):
             **prev_stats(m1, o1, self.Z[0]))
         dw(0, bn_dz(m1, o1, self.Z[0], False, G=self.G[1]), m1)
         dx(bn_dz(m1, o1, self.Z[0], True, G=self.G[1]), m1, net.c_pad, epilogue=1, dfeat=_ptr(self.dfeat), feat_c=net.c_pad,
-           row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]), act_c=0, grp_per_sample=1)
+           row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]), act_c=0, grp_per_sample=self.M)
         plan.call("gad_grad_from_arena", fl.gacc, fl.m2p, fl.n, self.grad, 0)
         return plan
 

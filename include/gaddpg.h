@@ -67,7 +67,21 @@ const char* gad_last_error(void);          /* thread-local description of the la
  * 0: v_mfma_f32_32x32x2_f32 throughout.  Non-zero: a mask of kernel families that form every FP32 product from split-bf16
  * terms on v_mfma_f32_32x32x16_bf16 with f32 accumulation (GAD_SPLIT_* below; 1 = every family that has the form).  A launch
  * takes the split form only if its family's bit is set AND the call carries the weight mirror it needs (W_split /
- * W_split_t; the streaming SA1 kernels split W themselves); otherwise it runs the FP32-MFMA kernel.                     */
+ * W_split_t; the streaming SA1 kernels split W themselves); otherwise it runs the FP32-MFMA kernel.
+ * "deterministic" [0]: 1 = every entry point either returns a result that is bit-identical whatever the launch grid, the
+ * grid-rows hints, the interleaving of streams or the timing, or refuses with GAD_ERR_UNSUPPORTED (gad_gemm_fwd mode 2; a scatter
+ * epilogue with more than one group or with previous-layer statistics).  The layer GEMMs take the generic 64 x 64 tile kernels
+ * only (no streaming / wide / skinny / split-bf16 family; gad_gemm_bwd = gad_gemm_dw then gad_gemm_dx); grid-rows hints are
+ * ignored; per-workgroup partial sums (BatchNorm statistics, dbeta / dgamma, split dW, sums of squares) are stored into slots of
+ * a grid-independent index and added by one ordered reduce (slot order, f64) into replica 0 of the statistics or into the arena
+ * -- replicas 1..3 receive nothing; the gathered first layer's input gradient is stored per row, then dfeat is accumulated over
+ * runs of rows that share no point (found from row_pt / row_grp alone), each run in ascending row order, and daction per sample
+ * (row_grp / grp_per_sample, as in the default mode) in ascending row order; gad_group_points_grad / gad_gather_points_grad
+ * apply their entries in (m, s) order.  Launches that add into one accumulator must still be ordered by the caller (one
+ * stream, or event edges).  The slot and row buffers are library-owned device memory per stream, allocated on first use,
+ * grown on demand (a growing call synchronises its stream: do not capture a graph before one uncaptured call per shape) and
+ * freed when the option is set back to 0; setting it to 1 allocates nothing.  Results differ from the default mode's by
+ * summation order only.                                                                                                      */
 #define GAD_SPLIT_ALL 1
 #define GAD_SPLIT_FWD_STREAM 2
 #define GAD_SPLIT_FWD_WIDE 4
