@@ -6,6 +6,12 @@
 // also mirrored into the packed, padded compute layout the GEMMs read (no separate repack pass).
 #include "common.hpp"
 
+__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
+    return v;
+}
+
 __global__ __launch_bounds__(256) void grad_from_arena_kernel(const double* __restrict__ gacc,
                                                               const int32_t* __restrict__ m2p, int n,
                                                               float* __restrict__ grad, int accumulate) {
@@ -104,16 +110,17 @@ extern "C" int gad_sumsq(const float* grad, int n, double* out, void* stream) {
     return GAD_OK;
 }
 
-// out[s] = max |x| over segment s.  Non-negative floats order like their bit patterns.
+// out[s] = max |x| over segment s.  Non-negative floats order like their bit patterns, and the pattern of |NaN| lies above
+// +inf's: the maximum is taken on the patterns throughout, so a NaN in the segment comes out as NaN (torch.abs(x).max()).
 __global__ __launch_bounds__(256) void absmax_segments_kernel(const float* __restrict__ x,
                                                               const int32_t* __restrict__ seg_off,
                                                               float* __restrict__ out) {
     const int s = blockIdx.y;
     const int lo = seg_off[s], hi = seg_off[s + 1];
-    float m = 0.f;
-    for (int i = lo + blockIdx.x * 256 + threadIdx.x; i < hi; i += gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned int*>(out + s), __float_as_uint(m));
+    unsigned m = 0u;
+    for (int i = lo + blockIdx.x * 256 + threadIdx.x; i < hi; i += gridDim.x * 256) m = max(m, __float_as_uint(fabsf(x[i])));
+    m = wave_max_u(m);
+    if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned int*>(out + s), m);
 }
 
 extern "C" int gad_absmax_segments(const float* x, const int32_t* seg_off, int n_seg, float* out, void* stream) {
@@ -127,7 +134,9 @@ extern "C" int gad_absmax_segments(const float* x, const int32_t* seg_off, int n
     return GAD_OK;
 }
 
-// hyper: {lr, beta1, beta2, eps, weight_decay, 1-beta1^t, sqrt(1-beta2^t), grad_scale}
+// hyper: {lr, beta1, beta2, eps, weight_decay, 1-beta1^t, sqrt(1-beta2^t), grad_scale, 1-beta1, 1-beta2} (GAD_ADAM_HYPER floats).
+// 1 - beta arrives from the host, formed in double: 1.f - float(0.999) is 1.29e-5 off float(0.001), which would sit in every
+// increment of exp_avg_sq.
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ grad,
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    const uint8_t* __restrict__ active,
@@ -138,7 +147,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
     if (i >= n) return;
     if (active && !active[i]) return;
     const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], bc1 = hyper[5],
-                sbc2 = hyper[6];
+                sbc2 = hyper[6], omb1 = hyper[8], omb2 = hyper[9];
     float coef = hyper[7];
     if (clip_sumsq) {
         const float c = clip_max / ((float)sqrt(*clip_sumsq) + 1e-6f);     // torch clip_grad_norm_
@@ -148,8 +157,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
     if (clip_sumsq) grad[i] = g;                                           // torch scales .grad in place
     const float pv = p[i];
     g = fmaf(wd, pv, g);
-    const float mi = b1 * m[i] + (1.f - b1) * g;
-    const float vi = b2 * v[i] + (1.f - b2) * g * g;
+    const float mi = b1 * m[i] + omb1 * g;
+    const float vi = b2 * v[i] + omb2 * g * g;
     m[i] = mi;
     v[i] = vi;
     const float denom = sqrtf(vi) / sbc2 + eps;
@@ -178,7 +187,7 @@ __global__ __launch_bounds__(256) void polyak_kernel(float* __restrict__ t, cons
     if (i >= n) return;
     const int k = sel ? sel[i] : 1;
     float nv;
-    if (k == 1) nv = t[i] * (1.f - tau) + s[i] * tau;
+    if (k == 1) nv = fmaf(tau, s[i], t[i] * (1.f - tau));                  // (spelled out: the same contraction as optim_jobs_kernel)
     else if (k == 2 && hard_enable) nv = s[i];
     else return;
     t[i] = nv;
@@ -212,17 +221,17 @@ __global__ __launch_bounds__(256) void optim_jobs_kernel(OptimJobs jobs) {
     const gad_optim_job& J = jobs.j[blockIdx.y];
     const int n = J.n;
     if (blockIdx.x == 0 && threadIdx.x < J.counter_n && J.counter) J.counter[threadIdx.x] += J.counter_add;
-    float lr = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f, wd = 0.f, bc1 = 1.f, sbc2 = 1.f, coef = 1.f;
+    float lr = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f, wd = 0.f, bc1 = 1.f, sbc2 = 1.f, coef = 1.f, omb1 = 1.f, omb2 = 1.f;
     const bool adam = J.hyper != nullptr;
     if (adam) {
         lr = J.hyper[0]; b1 = J.hyper[1]; b2 = J.hyper[2]; eps = J.hyper[3]; wd = J.hyper[4]; bc1 = J.hyper[5]; sbc2 = J.hyper[6];
-        coef = J.hyper[7];
+        coef = J.hyper[7]; omb1 = J.hyper[8]; omb2 = J.hyper[9];
         if (J.clip_sumsq) {
             const float c = J.clip_max / ((float)sqrt(*J.clip_sumsq) + 1e-6f);     // torch clip_grad_norm_
             coef *= c < 1.f ? c : 1.f;
         }
     }
-    float amax_p = 0.f, amax_g = 0.f;
+    unsigned amax_p = 0u, amax_g = 0u;       // bit patterns of |.|: ordered like the values, |NaN| above +inf (a NaN is reported)
     // one element: everything it reads arrives in registers (g, pv, m, v, the packed index jm, the arena value ga, the
     // target's value tv / selector k / packed index jt), everything it writes leaves through the flags -- so the body is the
     // same arithmetic for the scalar tail and for the 4-wide main loop
@@ -236,23 +245,23 @@ __global__ __launch_bounds__(256) void optim_jobs_kernel(OptimJobs jobs) {
             o.w_g = true;
         }
         if (adam && act) {
-            g *= coef;
-            if (J.clip_sumsq) o.w_g = true;                                        // torch scales .grad in place
-            float gw = fmaf(wd, pv, g);
-            const float mi = b1 * m + (1.f - b1) * gw;
-            const float vi = b2 * v + (1.f - b2) * gw * gw;
+            const float gs = g * coef;
+            if (J.clip_sumsq) { g = gs; o.w_g = true; }                            // torch scales .grad in place (only clip_grad_norm_ does)
+            float gw = fmaf(wd, pv, gs);
+            const float mi = b1 * m + omb1 * gw;
+            const float vi = b2 * v + omb2 * gw * gw;
             m = mi; v = vi;
             const float denom = sqrtf(vi) / sbc2 + eps;
             pv = pv - (lr / bc1) * (mi / denom);
             o.w_p = true;
         }
         if (J.target) {
-            if (k == 1) { tv = tv * (1.f - J.tau) + pv * J.tau; o.w_t = true; }
+            if (k == 1) { tv = fmaf(J.tau, pv, tv * (1.f - J.tau)); o.w_t = true; }     // (as polyak_kernel, bit for bit)
             else if (k == 2 && J.hard_enable) { tv = pv; o.w_t = true; }
         }
         o.g = g; o.pv = pv; o.m = m; o.v = v; o.tv = tv;
-        amax_p = fmaxf(amax_p, fabsf(pv));
-        amax_g = fmaxf(amax_g, fabsf(g));
+        amax_p = max(amax_p, __float_as_uint(fabsf(pv)));
+        if (act) amax_g = max(amax_g, __float_as_uint(fabsf(g)));                  // (an inactive element: .grad is None, counts 0)
         return o;
     };
     // main loop: four consecutive elements per thread, every stream a 16-byte access (the launch is latency-bound: with one
@@ -332,22 +341,21 @@ __global__ __launch_bounds__(256) void optim_jobs_kernel(OptimJobs jobs) {
     // statistics: one atomic per workgroup that had elements, spread over GAD_ABSMAX_SLOTS addresses (a same-address
     // device atomic costs ~25 ns: 4096 wavefronts on one slot were 0.1 ms)
     if ((J.absmax_p || J.absmax_grad) && (int)(blockIdx.x * 1024) < n) {
-        __shared__ float red[2][4];
-        amax_p = wave_max(amax_p);
-        amax_g = wave_max(amax_g);
+        __shared__ unsigned red[2][4];
+        amax_p = wave_max_u(amax_p);
+        amax_g = wave_max_u(amax_g);
         if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = amax_p; red[1][threadIdx.x >> 6] = amax_g; }
         __syncthreads();
         if (threadIdx.x == 0) {
             const int slot = blockIdx.x % GAD_ABSMAX_SLOTS;
             // look before the atomic (a relaxed device-scope load): once a few workgroups have posted, most find their
             // maximum already covered and skip the same-address atomic
-            auto post = [&](float* base, float v) {
+            auto post = [&](float* base, unsigned bits) {
                 unsigned* p = reinterpret_cast<unsigned int*>(base) + slot;
-                const unsigned bits = __float_as_uint(v);
                 if (bits > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, bits);
             };
-            if (J.absmax_p) post(J.absmax_p, fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3])));
-            if (J.absmax_grad) post(J.absmax_grad, fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3])));
+            if (J.absmax_p) post(J.absmax_p, max(max(red[0][0], red[0][1]), max(red[0][2], red[0][3])));
+            if (J.absmax_grad) post(J.absmax_grad, max(max(red[1][0], red[1][1]), max(red[1][2], red[1][3])));
         }
     }
 }

@@ -46,6 +46,7 @@ class MatSpec(object):
         self.bn_index = -1                                 # index into the per-pass BN vectors
 
 
+ADAM_HYPER = 10           # floats of the Adam scalar block (include/gaddpg.h GAD_ADAM_HYPER)
 HOST_RING = 4             # steps the host may run ahead of the GPU (pinned staging blocks per FlatNet / FusedRuntime)
 
 
@@ -108,10 +109,10 @@ class FlatNet(object):
                 o = off_of[id(p)]
                 active[o:o + p.numel()] = 0
         self.active = torch.from_numpy(active).to(device)
-        self.hyper = torch.zeros(8, **f32)                 # {lr,b1,b2,eps,wd,bc1,sqrt(bc2),grad_scale}
+        self.hyper = torch.zeros(ADAM_HYPER, **f32)        # {lr,b1,b2,eps,wd,bc1,sqrt(bc2),grad_scale,1-b1,1-b2}
         # pinned host blocks for the scalars, one per in-flight step (runtime.HOST_RING): the host may enqueue step
         # N+1 while the copy node of step N has not run yet
-        self.hyper_ring = torch.zeros(HOST_RING, 8, dtype=torch.float32)
+        self.hyper_ring = torch.zeros(HOST_RING, ADAM_HYPER, dtype=torch.float32)
         if device.type == "cuda":
             self.hyper_ring = self.hyper_ring.pin_memory()
         self.hyper_host = self.hyper_ring[0]
@@ -203,6 +204,7 @@ class FlatNet(object):
         h[5] = 1.0 - betas[0] ** t
         h[6] = float(np.sqrt(1.0 - betas[1] ** t))
         h[7] = grad_scale
+        h[8], h[9] = 1.0 - betas[0], 1.0 - betas[1]        # formed in double here: 1 - float32(beta) is 1.3e-5 off for 0.999
         if upload:
             self.hyper.copy_(self.hyper_host, non_blocking=True)
 

@@ -162,8 +162,8 @@ class FusedRuntime(object):
         self.fused_optim = self.has_critic and _os.environ.get("GAD_FUSED_OPTIM", "1") == "1"
         # this step's Adam scalars of every network: one pinned block per in-flight step, ONE upload
         self._opt_nets = [self.pol, self.enc] + ([self.venc, self.cr] if self.has_critic else [])
-        self.hyper_all = torch.zeros(len(self._opt_nets), 8, **f32)
-        self._hyper_ring = torch.zeros(R, len(self._opt_nets), 8, dtype=torch.float32).pin_memory()
+        self.hyper_all = torch.zeros(len(self._opt_nets), engine.ADAM_HYPER, **f32)
+        self._hyper_ring = torch.zeros(R, len(self._opt_nets), engine.ADAM_HYPER, dtype=torch.float32).pin_memory()
         for k, net in enumerate(self._opt_nets):
             net.flat.hyper = self.hyper_all[k]
         self.seg = {}

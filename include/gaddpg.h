@@ -48,7 +48,9 @@ int gad_abi_version(void);                 /* bumped on any signature change or 
                                             * W_split_t* of gad_gemm_dx_args), option "mfma_split" as a family mask;
                                             * 9: gad_transpose_batched; 10: gad_stream_priority;
                                             * 11: step replay (section H: gad_plan_*), gad_copy_buffers,
-                                            * action_bias in gad_policy_outputs)                                      */
+                                            * action_bias in gad_policy_outputs;
+                                            * 12: the Adam `hyper` block is GAD_ADAM_HYPER = 10 floats (1 - beta1, 1 - beta2
+                                            * appended)                                                                */
 /* diagnostics: which kernel family the last gad_gemm_fwd / _dx / _dw / _bwd call routed to ("gemm_fwd(stream)",
  * "gemm_dx(wide)", "gemm_bwd(stream)", "gemm_dw" = generic tile kernel, ...); bench.py labels its per-kernel table
  * with it instead of restating the routing rules.                                                  */
@@ -504,16 +506,20 @@ int gad_grad_from_arena_sumsq(const double* gacc, const int32_t* m2p, int n, flo
                               void* stream);
 /* sum of squares of grad[0..n) into *out (f64, atomically accumulated; zero it first)           */
 int gad_sumsq(const float* grad, int n, double* out, void* stream);
-/* max |x| over segments: out[s] = max |x[seg_off[s] .. seg_off[s+1])|                           */
+/* max |x| over segments: out[s] = max |x[seg_off[s] .. seg_off[s+1])| (0 for an empty segment; NaN if the segment holds a
+ * NaN, as torch.abs(x).max() reports it)                                                        */
 int gad_absmax_segments(const float* x, const int32_t* seg_off, int n_seg, float* out,
                         void* stream);
 /* Adam with L2 weight decay folded into the gradient (torch.optim.Adam, amsgrad=False), over a
- * flat buffer; `hyper` is a device array {lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2,
- * grad_scale}; active[i]==0 skips an element (parameters that never receive a gradient);
+ * flat buffer; `hyper` is a device array of GAD_ADAM_HYPER floats {lr, beta1, beta2, eps, weight_decay, bias_c1 =
+ * 1 - beta1^t, bias_c2 = sqrt(1 - beta2^t), grad_scale, 1 - beta1, 1 - beta2}, each formed in double on the host and
+ * rounded once (1 - beta is NOT derived from the rounded beta on the device: 1.f - float(0.999) is 1.29e-5 off
+ * float(0.001)); active[i]==0 skips an element (parameters that never receive a gradient);
  * clip_sumsq/clip_max (nullable) apply clip_grad_norm_ on the fly:
  *   g *= min(1, clip_max / (sqrt(*clip_sumsq) + 1e-6)).
  * Updated values are written to the master buffer p and mirrored into the packed compute buffer
  * packed[m2p[i]].                                                                               */
+#define GAD_ADAM_HYPER 10
 int gad_adam_step(float* p, const float* grad, float* exp_avg, float* exp_avg_sq,
                   const uint8_t* active, const int32_t* m2p, float* packed, int n,
                   const float* hyper, const double* clip_sumsq, float clip_max, void* stream);
@@ -524,8 +530,10 @@ int gad_polyak(float* target, const float* source, const uint8_t* sel, const int
  * .grad <- gradient arena (gad_grad_from_arena), Adam step with clip scaling and packed mirror (gad_adam_step; hyper ==
  * NULL: none), target-network update FROM THE UPDATED parameter (gad_polyak; target == NULL: none), max |p| / max |grad|
  * atomically maximised into absmax_p / absmax_grad (GAD_ABSMAX_SLOTS floats each, float bits, zeroed by the caller,
- * who takes the maximum of the slots), and counter[0..counter_n) += counter_add (BatchNorm num_batches_tracked).
- * Same arithmetic as the single-purpose entry points.  Alignment: p, grad, exp_avg, exp_avg_sq, m2p, target, target_m2p 16 bytes;
+ * who takes the maximum of the slots; max |p| over every element, max |grad| over the elements with active != 0 -- the
+ * reference's module_max_gradient counts a parameter without .grad as 0; a NaN element is reported as NaN, its bit pattern
+ * being the largest), and counter[0..counter_n) += counter_add once per launch (BatchNorm num_batches_tracked).
+ * Same arithmetic as the single-purpose entry points: bit-identical results (tests/test_gpu_optim_kernels.py).  Alignment: p, grad, exp_avg, exp_avg_sq, m2p, target, target_m2p 16 bytes;
  * active, target_sel 4 bytes (four elements per access; GAD_ERR_SHAPE otherwise).                                       */
 #define GAD_MAX_OPTIM_JOBS 4
 #define GAD_ABSMAX_SLOTS 8

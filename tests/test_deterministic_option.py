@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_library_accepts_deterministic_option_and_abi_is_unchanged():
     L = hip.lib()
-    assert L.gad_abi_version() == 11
+    assert L.gad_abi_version() == 12
     try:
         assert L.gad_set_option(b"deterministic", 1) == 0
         assert L.gad_set_option(b"deterministic", 0) == 0

@@ -281,7 +281,7 @@ def test_target_noise_and_optimizer_kernels():
     ref_p = torch.nn.Parameter(p0.clone())
     opt = torch.optim.Adam([ref_p], lr=3e-4, eps=1e-5, weight_decay=1e-5)
     p = p0.clone().cuda(); m = torch.zeros(n, device="cuda"); v = torch.zeros(n, device="cuda")
-    hyper = torch.zeros(8, device="cuda")
+    hyper = torch.zeros(10, device="cuda")
     for t in range(1, 4):
         g = torch.tensor(rng.normal(size=n) * (10.0 if t == 2 else 0.01), dtype=torch.float32)
         ref_p.grad = g.clone()
@@ -290,7 +290,7 @@ def test_target_noise_and_optimizer_kernels():
         gd = g.clone().cuda()
         ss = torch.zeros(1, dtype=torch.float64, device="cuda")
         hip.call("gad_sumsq", gd, n, ss)
-        hyper.copy_(torch.tensor([3e-4, 0.9, 0.999, 1e-5, 1e-5, 1 - 0.9 ** t, np.sqrt(1 - 0.999 ** t), 1.0]))
+        hyper.copy_(torch.tensor([3e-4, 0.9, 0.999, 1e-5, 1e-5, 1 - 0.9 ** t, np.sqrt(1 - 0.999 ** t), 1.0, 1 - 0.9, 1 - 0.999]))
         hip.call("gad_adam_step", p, gd, m, v, None, None, None, n, hyper, ss, 0.5)
         assert_close(gd.cpu().numpy(), ref_p.grad.numpy(), 1e-5, 1e-9, "clipped grad step %d" % t)
         assert_close(p.cpu().numpy(), ref_p.detach().numpy(), 1e-5, 1e-7, "adam step %d" % t)
