@@ -103,6 +103,16 @@ class BaseMemory(object):
     def reset(self):
         self.cur_idx = 0
         self.is_full = False
+        self.mark_rewritten()
+
+    def mark_rewritten(self):
+        """tell the mirrors of this buffer that its content changed by something other than push() / add_episode() -- reset,
+        load, arrays written directly: `written_slots` then answers "everything" instead of a list of slots"""
+        self.write_epoch = getattr(self, "write_epoch", 0) + 1
+
+    def write_stamp(self):
+        """(write_epoch, cur_idx, total_env_step, is_full): what `written_slots` needs to know of the cursor"""
+        return (int(getattr(self, "write_epoch", 0)), int(self.cur_idx), int(self.total_env_step), bool(self.is_full))
 
     # ------------------------------------------------------------------ sampling (A1)
     def draw_indices(self, batch_size, rng=None):
@@ -210,9 +220,9 @@ class BaseMemory(object):
         increment_idx = np.minimum(episode_end, batch_idx + 1).astype(np.int64)
         n = len(batch_idx)
         goal = np.array([pack_pose_rot_first(se3_inverse(self.state_pose[batch_idx[i]]).dot(self.state_pose[episode_end[i]]))
-                         for i in range(n)])
+                         for i in range(n)]).reshape(n, 7)                     # (n = 0: an empty batch keeps its columns)
         next_goal = np.array([pack_pose_rot_first(se3_inverse(self.state_pose[increment_idx[i]]).dot(self.state_pose[episode_end[i]]))
-                              for i in range(n)])
+                              for i in range(n)]).reshape(n, 7)
         return mask, goal, next_goal
 
     def set_onpolicy_goal(self, data, batch_idx, vis=False):
@@ -311,6 +321,7 @@ class BaseMemory(object):
         self.is_full = bool(data["is_full"]) and self.cur_idx >= self.buffer_size - 1
         self.cur_idx = self.upper_idx()
         self.recompute_return_with_gamma()
+        self.mark_rewritten()
 
     # ------------------------------------------------------------------ returns
     def recompute_return_with_gamma(self):
@@ -328,3 +339,44 @@ class BaseMemory(object):
 
 
 ReplayMemory = BaseMemory
+
+
+def sample_mixed(memories, sizes, rng=None, batch_idx=None):
+    """One minibatch from several buffers, as the reference's learner forms it (core/trainer.py:212-232: batch_size rows of the
+    expert buffer, int(batch_size * online_buffer_ratio) rows of the online buffer): memories[i].sample(sizes[i]) for each
+    memory IN LIST ORDER (so one `rng` is consumed expert first), then every key whose value in the first dict is an np.ndarray
+    and which the other dicts hold too is concatenated along axis 0, the first memory's rows first.  batch_idx: one index
+    array per memory instead of drawing.  A size of 0 contributes no rows."""
+    if len(memories) != len(sizes) or len(memories) < 1:
+        raise ValueError("sample_mixed: %d memories, %d sizes" % (len(memories), len(sizes)))
+    if batch_idx is not None and len(batch_idx) != len(memories):
+        raise ValueError("sample_mixed: batch_idx needs one index array per memory")
+    parts = [m.sample(int(n), rng=rng, batch_idx=None if batch_idx is None else np.asarray(batch_idx[i], dtype=np.int64))
+             for i, (m, n) in enumerate(zip(memories, sizes))]
+    first, rest = parts[0], parts[1:]
+    return {k: np.concatenate([p[k] for p in parts], axis=0) for k in first
+            if type(first[k]) is np.ndarray and all(k in p for p in rest)}
+
+
+def written_slots(old_stamp, new_stamp, capacity, buffer_start_idx):
+    """The slots push() wrote between two BaseMemory.write_stamp() values, from the cursor rule alone (slot = cur_idx %
+    capacity, then cur_idx + 1, wrapping to buffer_start_idx at the end; total_env_step counts the stored transitions):
+    a sorted int64 array without repeats, or None when the stamps are not explained by pushes alone (reset / load / direct
+    writes bump write_epoch; more pushes than the buffer holds; a cursor the walk does not arrive at) -- None means
+    "everything may have changed".  Host arithmetic only."""
+    if old_stamp is None or new_stamp is None or old_stamp[0] != new_stamp[0]:
+        return None
+    capacity, start = int(capacity), int(buffer_start_idx)
+    n = int(new_stamp[2]) - int(old_stamp[2])
+    if n < 0 or n > capacity or (old_stamp[3] and not new_stamp[3]):
+        return None
+    cur = int(old_stamp[1])
+    slots = np.empty(n, dtype=np.int64)
+    for k in range(n):
+        slots[k] = cur % capacity
+        cur += 1
+        if cur >= capacity or cur < start:
+            cur = start
+    if cur != int(new_stamp[1]):
+        return None
+    return np.unique(slots)

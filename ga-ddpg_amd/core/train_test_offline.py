@@ -19,7 +19,7 @@ import time
 
 import numpy as np
 
-from .replay_memory import BaseMemory
+from .replay_memory import BaseMemory, sample_mixed
 from .utils import get_loss_info_dict, migrate_model
 
 LOG_INTERVAL = 4
@@ -58,29 +58,34 @@ def device_replay_fits(memory, reserve=0.5):
     return need < reserve * free
 
 
-def _write_stamp(memory):
-    """changes whenever a transition was written since the stamp was taken (push / add_episode / load)"""
-    return (int(memory.cur_idx), bool(memory.is_full), int(memory.total_env_step))
-
-
 def device_mirror(memory):
     """the HBM mirror of `memory`, built ONCE per memory object and kept on it (a caller that alternates
     train_off_policy with buffer writes must neither re-allocate GBs per call nor train on a stale snapshot): a later call
-    re-uploads only when the buffer was written in between (everything up to upper_idx(): writes wrap around)."""
+    uploads what was written in between -- DeviceReplay.sync_writes(): the clouds of the slots push() wrote, everything up to
+    upper_idx() when the buffer changed in any other way."""
     from .device_replay import DeviceReplay
-    ent = getattr(memory, "_gad_device_mirror", None)
-    stamp = _write_stamp(memory)
-    if ent is None or ent[0].cap != memory.point_state.shape[0]:
-        ent = [DeviceReplay(memory), stamp]
-        memory._gad_device_mirror = ent
-    elif ent[1] != stamp:
-        ent[0].refresh(0, memory.upper_idx())
-        ent[1] = stamp
-    return ent[0]
+    dmem = getattr(memory, "_gad_device_mirror", None)
+    if dmem is None or dmem.cap != memory.point_state.shape[0]:
+        dmem = DeviceReplay(memory)
+        memory._gad_device_mirror = dmem
+    else:
+        dmem.sync_writes()
+    return dmem
+
+
+def mixed_device_mirror(memory, online_memory, n_expert, n_online):
+    """device_mirror() of both buffers + ONE MixedDeviceReplay for the pair and the split, kept on the expert memory"""
+    from .device_replay import MixedDeviceReplay
+    d0, d1 = device_mirror(memory), device_mirror(online_memory)
+    ent = getattr(memory, "_gad_mixed_mirror", None)
+    if ent is None or ent[0] is not d0 or ent[1] is not d1 or ent[2:4] != (int(n_expert), int(n_online)):
+        ent = (d0, d1, int(n_expert), int(n_online), MixedDeviceReplay([(d0, n_expert), (d1, n_online)]))
+        memory._gad_mixed_mirror = ent
+    return ent[4]
 
 
 def train_off_policy(agent, memory, config, model_output_dir=None, save_model=False, log=None, max_epochs=None,
-                     sample=None, run_ahead=False, device_replay="auto", rng=None):
+                     sample=None, run_ahead=False, device_replay="auto", rng=None, online_memory=None):
     """The reference's train_off_policy() (:107-161) over an agent and a filled replay memory.
     config = cfg.RL_TRAIN (updates_per_step, batch_size, save_epoch, max_epoch).  `sample(batch_size)` overrides
     memory.sample (device-resident replay, prefetching samplers).  Returns the per-key loss history (deques, as the
@@ -88,8 +93,24 @@ def train_off_policy(agent, memory, config, model_output_dir=None, save_model=Fa
     run_ahead: enqueue the `updates_per_step` updates of an epoch without waiting for each (update_parameters(sync=False));
     their losses are read at the end of the epoch, the host samples / stages the next minibatch while the GPU works.
     rng: a numpy Generator / RandomState for the minibatch indices of the mirrored path (default: the global np.random
-    stream, which is what the reference's memory.sample draws from)."""
+    stream, which is what the reference's memory.sample draws from).
+    online_memory: a second BaseMemory.  With config.onpolicy and n_on = int(batch_size * online_buffer_ratio) > 0 every
+    update trains on batch_size rows of `memory` followed by n_on rows of `online_memory` (the reference learner's batch,
+    core/trainer.py:212-232); the indices are drawn expert first.  Both buffers are mirrored in HBM under the same
+    `device_replay` rule (one gather launch per minibatch), else the host forms the batch (replay_memory.sample_mixed)."""
     losses = get_loss_info_dict()
+    n_on = int(config.batch_size * config.online_buffer_ratio) if (online_memory is not None and config.onpolicy) else 0
+    total_batch = int(config.batch_size) + n_on
+    if n_on > 0 and sample is None:
+        if device_replay and hasattr(agent, "runtime") and (
+                device_replay is True or (device_replay_fits(memory) and device_replay_fits(online_memory))):
+            mixed = mixed_device_mirror(memory, online_memory, config.batch_size, n_on)
+            sample = lambda batch_size: mixed.sample_lazy(rng=rng)                  # noqa: E731
+            if log is not None:
+                log("replay buffers mirrored in HBM (%d expert + %d online transitions); device_replay=False keeps the host "
+                    "sampling path" % (len(memory), len(online_memory)))
+        else:
+            sample = lambda batch_size: sample_mixed((memory, online_memory), (batch_size, n_on), rng=rng)   # noqa: E731
     if sample is None and device_replay and (device_replay is True or device_replay_fits(memory)) and hasattr(agent, "runtime"):
         # default feeding path (VERDICT r03 item 8): the buffer mirrored in HBM, indices drawn on the host with the
         # reference's arithmetic and random stream (np.random, as memory.sample uses), ONE gather launch per minibatch --
@@ -144,7 +165,7 @@ def train_off_policy(agent, memory, config, model_output_dir=None, save_model=Fa
         epochs = epoch
         if log is not None:
             log("epoch: {} updates: {} lr: {:.6f} network time: {:.2f} data time: {:.2f} batch size: {}".format(
-                epoch, agent.update_step, lrs["policy_lr"], network_time, data_time, config.batch_size))
+                epoch, agent.update_step, lrs["policy_lr"], network_time, data_time, total_batch))
             rows = [(name, float(np.mean(list(h)))) for name, h in losses.items() if np.mean(list(h)) != 0]
             try:
                 import tabulate
@@ -163,6 +184,9 @@ def main(argv=None):
     ap.add_argument("--policy", default=None, help="DDPG | BC (default: from cfg.RL_TRAIN.RL)")
     ap.add_argument("--data", default=None, help="directory holding the replay .npz written by BaseMemory.save (reference "
                                                  "format, file name = cfg RL_SAVE_DATA_NAME); default: a seeded synthetic buffer")
+    ap.add_argument("--online_data", default=None, help="directory holding a second replay .npz, the ONLINE buffer: with "
+                                                        "RL_TRAIN.onpolicy every update adds int(batch_size * online_buffer_ratio) "
+                                                        "of its rows to the minibatch, behind the expert rows")
     ap.add_argument("--buffer", type=int, default=20000, help="transitions of the synthetic buffer")
     ap.add_argument("--pretrained", default=None)
     ap.add_argument("--model_surfix", default="latest")
@@ -184,8 +208,12 @@ def main(argv=None):
         from ..synth_data import fill_synthetic_buffer
         memory = BaseMemory(args.buffer, config, point_dtype=np.float32)
         fill_synthetic_buffer(memory, args.buffer, seed=20260928)
+    online = None
+    if args.online_data:
+        online = BaseMemory(int(cfg.OFFLINE_RL_MEMORY_SIZE) + 1, config, name="online")
+        online.load(args.online_data, int(cfg.OFFLINE_RL_MEMORY_SIZE))
     losses, epochs = train_off_policy(agent, memory, config, args.output_dir, args.save_model, log=print,
-                                      device_replay=False if args.host_replay else "auto")
+                                      device_replay=False if args.host_replay else "auto", online_memory=online)
     if args.save_model:
         agent.save_model(agent.update_step, output_dir=args.output_dir)
     return losses, epochs

@@ -450,6 +450,80 @@ extern "C" int gad_replay_gather(const gad_replay_gather_args* a, void* stream) 
     return GAD_OK;
 }
 
+// The same gather over up to GAD_REPLAY_MAX_SRC buffers (the reference's learner concatenates an expert and an online
+// minibatch, core/trainer.py:212-232): output row b reads source s with row_start[s] <= b < row_start[s + 1], its indices are
+// local to that source.  blockIdx.y = output row, so the source lookup is uniform per workgroup.  V = float2 (the 8-byte
+// path of the kernel above) or float4 (chosen on the host when cloud_elems % 4 == 0 and every cloud pointer is 16-byte
+// aligned).  The hindsight goals of DeviceReplay ride in `relabel` (B, 8) = [goal (7) | flag] and replace the gathered goal
+// where the flag is > 0.
+template <typename V>
+__global__ __launch_bounds__(256) void replay_gather_multi_kernel(gad_replay_mix_args a) {
+    const int b = blockIdx.y;
+    int s = 0;
+#pragma unroll
+    for (int k = 1; k < GAD_REPLAY_MAX_SRC; ++k) s += (k < a.n_src && b >= a.row_start[k]) ? 1 : 0;   // empty sources are stepped over
+    const gad_replay_src S = a.src[s];
+    const long long i = a.idx[b], n = a.nxt[b];
+    constexpr int W = (int)(sizeof(V) / sizeof(float));
+    const int vecs = a.cloud_elems / W;
+    const V* s0 = reinterpret_cast<const V*>(S.point_state + (size_t)i * a.cloud_elems);
+    const V* s1 = reinterpret_cast<const V*>(S.point_state + (size_t)n * a.cloud_elems);
+    V* d0 = reinterpret_cast<V*>(a.out_point + (size_t)b * a.cloud_elems);
+    V* d1 = reinterpret_cast<V*>(a.out_next_point + (size_t)b * a.cloud_elems);
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < vecs; p += gridDim.x * 256) {
+        d0[p] = s0[p];
+        if (a.out_next_point) d1[p] = s1[p];
+    }
+    if (blockIdx.x != 0) return;
+    const int t = threadIdx.x;
+    if (t < 6) { a.out_action[b * 6 + t] = S.action[i * 6 + t]; a.out_expert_action[b * 6 + t] = S.expert_action[i * 6 + t]; }
+    if (t < 7) {
+        const bool hindsight = a.relabel && a.relabel[b * 8 + 7] > 0.f;
+        a.out_goal[b * 7 + t] = hindsight ? a.relabel[b * 8 + t] : S.goal[i * 7 + t];
+    }
+    if (t == 8) a.out_reward[b] = S.reward[i];
+    if (t == 9) a.out_return[b] = S.returns[i];
+    if (t == 10) a.out_mask[b] = S.terminal[i];
+    if (t == 11) a.out_expert_flag[b] = S.expert_flags[i];
+    if (t == 12) a.out_perturb_flag[b] = S.perturb_flags[i];
+    if (t == 13) {
+        const float tm = S.timestep[a.end[b]] + 1.f - S.timestep[i];     // remaining steps of the episode
+        a.out_time[b] = tm;
+        a.out_time_m1[b] = tm - 1.f;
+    }
+}
+
+extern "C" int gad_replay_gather_multi(const gad_replay_mix_args* a, void* stream) {
+    GAD_REQUIRE(a, GAD_ERR_NULL, "replay_gather_multi: null arguments");
+    GAD_REQUIRE(a->n_src >= 1 && a->n_src <= GAD_REPLAY_MAX_SRC, GAD_ERR_SHAPE, "replay_gather_multi: n_src %d outside 1..%d",
+                a->n_src, GAD_REPLAY_MAX_SRC);
+    GAD_REQUIRE(a->B >= 1 && a->B <= 65535, GAD_ERR_SHAPE, "replay_gather_multi: B %d outside 1..65535", a->B);
+    GAD_REQUIRE(a->cloud_elems >= 2 && a->cloud_elems % 2 == 0, GAD_ERR_SHAPE,
+                "replay_gather_multi: cloud_elems %d must be even and at least 2", a->cloud_elems);
+    GAD_REQUIRE(a->row_start[0] == 0 && a->row_start[a->n_src] == a->B, GAD_ERR_SHAPE,
+                "replay_gather_multi: row_start must run from 0 to B = %d, got %d .. %d", a->B, a->row_start[0], a->row_start[a->n_src]);
+    for (int s = 0; s < a->n_src; ++s)
+        GAD_REQUIRE(a->row_start[s + 1] >= a->row_start[s], GAD_ERR_SHAPE, "replay_gather_multi: row_start decreases at source %d", s);
+    GAD_REQUIRE(a->idx && a->nxt && a->end, GAD_ERR_NULL, "replay_gather_multi: null index vector");
+    GAD_REQUIRE(a->out_point && a->out_action && a->out_expert_action && a->out_goal && a->out_reward && a->out_return && a->out_mask &&
+                a->out_time && a->out_time_m1 && a->out_expert_flag && a->out_perturb_flag, GAD_ERR_NULL, "replay_gather_multi: null output");
+    bool wide = a->cloud_elems % 4 == 0 && (reinterpret_cast<size_t>(a->out_point) & 15) == 0 &&
+                (reinterpret_cast<size_t>(a->out_next_point) & 15) == 0;
+    for (int s = 0; s < a->n_src; ++s) {
+        if (a->row_start[s + 1] == a->row_start[s]) continue;            // owns no row: never read, may be all NULL
+        const gad_replay_src& S = a->src[s];
+        GAD_REQUIRE(S.point_state && S.action && S.expert_action && S.goal && S.reward && S.returns && S.terminal && S.timestep &&
+                    S.expert_flags && S.perturb_flags, GAD_ERR_NULL, "replay_gather_multi: null pointer in source %d", s);
+        wide = wide && (reinterpret_cast<size_t>(S.point_state) & 15) == 0;
+    }
+    if (wide)
+        hipLaunchKernelGGL(replay_gather_multi_kernel<float4>, dim3(4, a->B), dim3(256), 0, (hipStream_t)stream, *a);
+    else
+        hipLaunchKernelGGL(replay_gather_multi_kernel<float2>, dim3(4, a->B), dim3(256), 0, (hipStream_t)stream, *a);
+    GAD_CHECK_LAUNCH("replay_gather_multi");
+    return GAD_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // one launch clears up to six buffers (statistics, gradient arenas, scatter targets of a backward pass): each of
 // them used to be its own fill kernel at the head / in the middle of the pass's dependency chain

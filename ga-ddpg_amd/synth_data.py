@@ -99,6 +99,8 @@ def fill_synthetic_buffer(memory, n_transitions, seed=20260928, gamma=None):
     memory.cur_idx = n_transitions
     memory.total_env_step = n_transitions
     memory.is_full = n_transitions >= memory.buffer_size
+    if hasattr(memory, "mark_rewritten"):       # the arrays were written directly, not through push(): mirrors re-upload everything
+        memory.mark_rewritten()
     return memory
 
 

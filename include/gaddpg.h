@@ -50,7 +50,8 @@ int gad_abi_version(void);                 /* bumped on any signature change or 
                                             * 11: step replay (section H: gad_plan_*), gad_copy_buffers,
                                             * action_bias in gad_policy_outputs;
                                             * 12: the Adam `hyper` block is GAD_ADAM_HYPER = 10 floats (1 - beta1, 1 - beta2
-                                            * appended)                                                                */
+                                            * appended); added under 12 without a bump (no existing signature or struct
+                                            * layout changed): gad_replay_gather_multi                                  */
 /* diagnostics: which kernel family the last gad_gemm_fwd / _dx / _dw / _bwd call routed to ("gemm_fwd(stream)",
  * "gemm_dx(wide)", "gemm_bwd(stream)", "gemm_dw" = generic tile kernel, ...); bench.py labels its per-kernel table
  * with it instead of restating the routing rules.                                                  */
@@ -579,6 +580,9 @@ int gad_split_weights(const float* packed, const gad_split_layer* host_layers, i
  *    successor index, episode end -- stays on the host and is the reference's).  One launch fills the update
  *    step's input buffers: out_*[b] = src[idx[b]], next cloud = point_state[nxt[b]],
  *    time[b] = timestep[end[b]] + 1 - timestep[idx[b]], time_m1 = time - 1.
+ *    gad_replay_gather reads one buffer; gad_replay_gather_multi fills the same outputs from up to four buffers (the
+ *    expert + online minibatch of the reference's learner), each block of output rows from its own source, and folds the
+ *    hindsight-goal overwrite into the launch.
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t B;
@@ -596,6 +600,44 @@ typedef struct {
 } gad_replay_gather_args;
 
 int gad_replay_gather(const gad_replay_gather_args* host_args, void* stream);
+
+/* The same gather from up to GAD_REPLAY_MAX_SRC device-resident buffers in ONE launch: the reference's learner draws
+ * batch_size rows from the expert buffer and int(batch_size * online_buffer_ratio) rows from the online buffer and
+ * concatenates them key by key, expert rows first (core/trainer.py:212-232).  Output row b belongs to source s with
+ * row_start[s] <= b < row_start[s + 1] (row_start[0] = 0, non-decreasing, row_start[n_src] = B); idx[b], nxt[b] and end[b]
+ * are indices LOCAL to that source (end indexes its timestep).  A source that owns no row is never read and may be all NULL.
+ * All sources share cloud_elems.  Per-row arithmetic is gad_replay_gather's (time = timestep[end] + 1 - timestep[idx],
+ * time_m1 = time - 1); with n_src = 1 and relabel = NULL the outputs are bit-identical to it.
+ * relabel: NULL, or (B, 8) float32 rows [goal (7) | flag]: out_goal[b] = relabel[b, 0:7] where relabel[b, 7] > 0, else the
+ * gathered goal (the hindsight goals of reference core/replay_memory.py:233-249, formed on the host).
+ * Clouds move as 16-byte groups when cloud_elems % 4 == 0 and out_point, out_next_point and the point_state of every source
+ * that owns a row are 16-byte aligned, as 8-byte pairs otherwise (chosen per launch on the host; same bytes either way).
+ * Refused before any launch: NULL args (GAD_ERR_NULL); n_src outside 1..GAD_REPLAY_MAX_SRC, B outside 1..65535, cloud_elems
+ * odd or < 2, a row_start that does not run 0 .. B without decreasing (GAD_ERR_SHAPE); a NULL index vector, a NULL output other
+ * than out_next_point, a NULL pointer in a source that owns a row (GAD_ERR_NULL). */
+#define GAD_REPLAY_MAX_SRC 4
+typedef struct {
+    const float* point_state;            /* (cap, cloud_elems) */
+    const float* action; const float* expert_action;                      /* (cap, 6) */
+    const float* goal;                   /* (cap, 7) */
+    const float* reward; const float* returns; const float* terminal; const float* timestep;
+    const float* expert_flags; const float* perturb_flags;                /* (cap) */
+} gad_replay_src;
+typedef struct {
+    int32_t B;                           /* output rows = sum of the sources' shares */
+    int32_t cloud_elems;                 /* floats per transition of point_state, multiple of 2; the same for every source */
+    int32_t n_src;
+    int32_t row_start[GAD_REPLAY_MAX_SRC + 1];
+    gad_replay_src src[GAD_REPLAY_MAX_SRC];
+    const int64_t* idx; const int64_t* nxt; const int64_t* end;           /* (B) device index vectors, source-local */
+    const float* relabel;                /* (B, 8) or NULL */
+    float* out_point; float* out_next_point;                              /* (B, cloud_elems); out_next_point may be NULL */
+    float* out_action; float* out_expert_action; float* out_goal;
+    float* out_reward; float* out_return; float* out_mask; float* out_time; float* out_time_m1;
+    float* out_expert_flag; float* out_perturb_flag;
+} gad_replay_mix_args;
+
+int gad_replay_gather_multi(const gad_replay_mix_args* host_args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * G. housekeeping
