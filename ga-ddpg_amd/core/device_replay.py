@@ -14,10 +14,17 @@ test_device_replay_matches_host_sampling).
 
 `refresh(lo, hi)` re-uploads a slice after the host buffer was written to (online training).
 
-Hindsight relabelling (`memory.self_supervision` on a non-expert buffer, reference core/replay_memory.py:233-249,271-272): the
-relabelled goals are 4x4 pose algebra on B rows -- host work, done by the SAME BaseMemory.onpolicy_goals the host path
-uses -- and travel with the index vectors as a (B, 8) block [goal (7) | relabel flag]; the gather's goal rows are
-overwritten where the flag is set, so both paths train on the same goals.
+Hindsight relabelling (`memory.self_supervision` on a non-expert buffer, reference core/replay_memory.py:233-249,271-272) is
+4x4 pose algebra on B rows, in one of two modes chosen per mirror:
+  relabel="host" (default): the goals are formed by the SAME BaseMemory.onpolicy_goals the host path uses -- a Python loop with
+    an eigen-decomposition per row, at handle-draw time -- and travel with the index vectors as a (B, 8) block
+    [goal (7) | relabel flag]; the gather's goal rows are overwritten where the flag is set, so both paths train on
+    bit-identical goals.
+  relabel="device": the mirror also keeps `state_pose` (cap x 16 float32, 64 B a transition) and one gad_replay_relabel_goals
+    launch behind the gather forms the goals of the on-policy rows from it by a float32 closed form (include/gaddpg.h
+    section F); the host does no pose algebra.  Promise: rigid poses; goals equal the host's to float32 rounding, not bit for
+    bit (tests/test_gpu_device_relabel.py); expert rows and every other key stay bit-identical.
+A handle remembers the mode it was drawn in ("relabel_mode").
 """
 import numpy as np
 import torch
@@ -103,6 +110,20 @@ def _upload_stage_set(it, copy_stream, refresh_events, relabel):
     it["relabel"] = relabel
 
 
+def _launch_relabel(B, row_start, srcs, idx, end, goal):
+    """one gad_replay_relabel_goals launch on the current stream, behind the gather / index_select that wrote `goal` (B, 7):
+    srcs[s] = (state_pose, expert_flags) of a source whose on-policy rows get hindsight goals, or None"""
+    a = hip.ReplayRelabelArgs()
+    a.B, a.n_src = int(B), len(srcs)
+    for s, r in enumerate(row_start):
+        a.row_start[s] = int(r)
+    for s, src in enumerate(srcs):
+        if src is not None:
+            a.src[s].state_pose, a.src[s].expert_flags = hip.ptr(src[0]), hip.ptr(src[1])
+    a.idx, a.end, a.out_goal = hip.ptr(idx), hip.ptr(end), hip.ptr(goal)
+    hip.call_struct("gad_replay_relabel_goals", a)
+
+
 def _stage_set_used(it, stream):
     """the staging set is not rewritten before what was just enqueued on `stream` has read it"""
     if it["used"] is None:
@@ -112,8 +133,11 @@ def _stage_set_used(it, stream):
 
 
 class DeviceReplay(object):
-    def __init__(self, memory, device=None):
+    def __init__(self, memory, device=None, relabel="host"):
+        if relabel not in ("host", "device"):
+            raise ValueError("DeviceReplay: relabel must be \"host\" or \"device\", got %r" % (relabel,))
         self.memory = memory
+        self.relabel = relabel
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("DeviceReplay needs a GPU (the update path has no CPU fallback)")
@@ -123,6 +147,8 @@ class DeviceReplay(object):
         self.point_state = torch.empty(tuple(memory.point_state.shape), **f32)
         self.rows = {src: torch.empty(tuple(getattr(memory, src).shape), **f32) for src, _ in _ROW_KEYS}
         self.timestep = torch.empty(cap, **f32)
+        # relabel="device" only: the poses the hindsight goals are formed from (64 B a transition)
+        self.state_pose = torch.empty(cap, 16, **f32) if relabel == "device" else None
         self._stage = {}
         self._copy_stream = None
         self._ev_refresh = None
@@ -155,6 +181,8 @@ class DeviceReplay(object):
         for src, _ in _ROW_KEYS:
             self.rows[src][sl].copy_(torch.from_numpy(np.ascontiguousarray(getattr(m, src)[sl], dtype=np.float32)))
         self.timestep[sl].copy_(torch.from_numpy(np.ascontiguousarray(m.timestep[sl], dtype=np.float32)))
+        if self.state_pose is not None:
+            self.state_pose[sl].copy_(torch.from_numpy(np.ascontiguousarray(m.state_pose[sl], dtype=np.float32).reshape(-1, 16)))
 
     def _refreshed(self):
         if self._ev_refresh is None:
@@ -165,8 +193,8 @@ class DeviceReplay(object):
         """bring the mirror up to date after the host buffer was written (online training: rollouts land between epochs).
         Clouds -- 16.5 KB a transition, all but 0.6 % of the bytes -- go up for exactly the slots push() wrote since the last
         sync (replay_memory.written_slots, from the cursor stamps), as runs of neighbouring slots; the small row arrays
-        (104 B a transition) go up whole over [0, upper_idx()), which also carries add_episode's back-filled returns of
-        earlier slots.  Stamps that pushes alone do not explain (reset, load, direct writes announced by mark_rewritten(),
+        (104 B a transition, 168 B with the poses of relabel="device") go up whole over [0, upper_idx()), which also carries
+        add_episode's back-filled returns of earlier slots.  Stamps that pushes alone do not explain (reset, load, direct writes announced by mark_rewritten(),
         more pushes than the buffer holds) -> refresh(0, upper_idx()).  -> number of cloud rows uploaded."""
         m = self.memory
         stamp = _write_stamp(m)
@@ -202,6 +230,8 @@ class DeviceReplay(object):
         h = host.numpy()
         h[0], h[1], h[2] = idx, nxt, end
         relabel = self._relabels()
+        it["relabel_device"] = relabel and self.relabel == "device"      # formed behind the gather, from the mirrored poses
+        relabel = relabel and self.relabel == "host"
         if relabel:                              # hindsight goals of the on-policy rows (BaseMemory.post_process_batch)
             mask, goal, _ = self.memory.onpolicy_goals(idx)
             g = it["ghost"].numpy()
@@ -218,6 +248,12 @@ class DeviceReplay(object):
         g = it["gdev"]
         goal.copy_(torch.where(g[:, 7:8] > 0, g[:, :7], goal))
 
+    def _relabel_on_device(self, it, goal):
+        """goal rows of the on-policy rows <- hindsight goals formed from the mirrored poses (same stream as the gather that wrote
+        `goal`, whose index vectors the launch reads: call it before _stage_set_used)"""
+        dev = it["dev"]
+        _launch_relabel(dev.shape[1], (0, dev.shape[1]), [(self.state_pose, self.rows["expert_flags"])], dev[0], dev[2], goal)
+
     # ------------------------------------------------------------------ sampling
     def sample_lazy(self, batch_size, rng=None, batch_idx=None):
         """like sample(), but nothing is gathered yet: the returned dict carries the device index vectors and
@@ -232,7 +268,7 @@ class DeviceReplay(object):
         B = batch_idx.shape[0]
         dev, ev, it = self._indices3(batch_idx, nxt, end)
         return {"replay_gather": self, "idx": dev[0], "nxt": dev[1], "end": dev[2], "ready_event": ev, "_stage_set": it,
-                "batch_idx": np.uint8(batch_idx),
+                "relabel_mode": self.relabel, "batch_idx": np.uint8(batch_idx),
                 "point_state_batch": _Shape((B,) + tuple(self.point_state.shape[1:])),
                 "mask_counts": self._mask_counts(batch_idx)}
 
@@ -260,6 +296,8 @@ class DeviceReplay(object):
         it = lazy.get("_stage_set")
         if it is not None and it.get("relabel"):
             self._apply_relabel(it, dbuf["goal_batch"])
+        if it is not None and it.get("relabel_device"):
+            self._relabel_on_device(it, dbuf["goal_batch"])
         if it is not None:                       # the staging set is not rewritten before this gather has run
             _stage_set_used(it, cur)
 
@@ -301,6 +339,8 @@ class DeviceReplay(object):
         out["time_batch"] = self.timestep.index_select(0, d_end) + 1.0 - self.timestep.index_select(0, d_idx)
         if it.get("relabel"):
             self._apply_relabel(it, out["goal_batch"])
+        if it.get("relabel_device"):
+            self._relabel_on_device(it, out["goal_batch"])
         _stage_set_used(it, cur)                 # the index_selects above read the staging set's device block
         out["batch_idx"] = np.uint8(batch_idx)
         out["mask_counts"] = self._mask_counts(batch_idx)
@@ -314,7 +354,9 @@ class MixedDeviceReplay(object):
     replay_memory.sample_mixed).  Up to hip.REPLAY_MAX_SRC parts; a part of 0 rows is allowed.  Index arithmetic is each
     memory's own draw_indices / next_indices / episode_map, drawn in list order from one `rng`, so a minibatch equals
     sample_mixed with the same per-part indices.  Hindsight goals are formed for the rows of the parts whose memory relabels
-    (DeviceReplay._relabels) only.  One gad_replay_gather_multi launch fills the step's input buffers (or sample()'s
+    (DeviceReplay._relabels) only, in each part's own mode (DeviceReplay(relabel=...)): relabel="host" parts fill the staged (B, 8)
+    block the gather applies, relabel="device" parts get ONE gad_replay_relabel_goals launch behind the gather (none when no such
+    part relabels).  One gad_replay_gather_multi launch fills the step's input buffers (or sample()'s
     tensors); the handle of sample_lazy() follows DeviceReplay's contract, so FusedRuntime.upload / prefetch_inputs,
     PrefetchSampler and train_off_policy's lookahead take it as they take a DeviceReplay's."""
 
@@ -362,12 +404,15 @@ class MixedDeviceReplay(object):
         it = _take_stage_set(self._stage, self.B, self.device, self.RING)
         h, g = it["host"].numpy(), it["ghost"].numpy()
         relabel = False
-        for d, ix, lo, hi in zip(self.parts, idx, self.row_start[:-1], self.row_start[1:]):
+        on_device = [False] * len(self.parts)    # parts whose hindsight goals are formed behind the gather
+        for s, (d, ix, lo, hi) in enumerate(zip(self.parts, idx, self.row_start[:-1], self.row_start[1:])):
             if hi == lo:
                 continue
             m = d.memory
             h[0, lo:hi], h[1, lo:hi], h[2, lo:hi] = ix, m.next_indices(ix), m.episode_map[ix]
-            if d._relabels():                    # hindsight goals of this part's on-policy rows
+            if d._relabels() and d.relabel == "device":
+                on_device[s] = True
+            elif d._relabels():                  # hindsight goals of this part's on-policy rows
                 if not relabel:
                     g[:, 7] = 0.0                # every other row keeps its stored goal
                     relabel = True
@@ -377,13 +422,14 @@ class MixedDeviceReplay(object):
         if self._copy_stream is None:
             self._copy_stream = torch.cuda.Stream(device=self.device)
         _upload_stage_set(it, self._copy_stream, [d._ev_refresh for d in self.parts], relabel)
+        it["relabel_device"] = on_device if any(on_device) else None
         return it
 
     def _handle(self, idx, it):
         dev = it["dev"]
         counts = sum(d._mask_counts(ix) for d, ix in zip(self.parts, idx))
         return {"replay_gather": self, "idx": dev[0], "nxt": dev[1], "end": dev[2], "ready_event": it["copied"], "_stage_set": it,
-                "batch_idx": np.concatenate([np.uint8(ix) for ix in idx]),
+                "relabel_mode": tuple(d.relabel for d in self.parts), "batch_idx": np.concatenate([np.uint8(ix) for ix in idx]),
                 "point_state_batch": _Shape((self.B,) + self.cloud_shape),
                 "mask_counts": counts}
 
@@ -422,6 +468,10 @@ class MixedDeviceReplay(object):
                          ("out_perturb_flag", "perturb_flag_batch")):
             setattr(a, dst, hip.ptr(dbuf[key]))
         hip.call_struct("gad_replay_gather_multi", a)
+        if it is not None and it.get("relabel_device"):      # reads idx / end of the set's device block: before `used` records
+            _launch_relabel(self.B, self.row_start, [(d.state_pose, d.rows["expert_flags"]) if on else None
+                                                     for d, on in zip(self.parts, it["relabel_device"])],
+                            lazy["idx"], lazy["end"], dbuf["goal_batch"])
         if it is not None:
             _stage_set_used(it, cur)
 

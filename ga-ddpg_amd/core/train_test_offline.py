@@ -11,7 +11,8 @@ update_step >= max_epoch; batch size = cfg.OFFLINE_BATCH_SIZE (:351); a loss tab
 SURVEY section 2): the Ray harness, tensorboard writer, the test()/rollout branch and the PyBullet environment.
 The replay buffer is mirrored in HBM by default when it fits (`device_replay="auto"`): sampling then costs one
 gather launch instead of a 17 MB host gather + PCIe upload per step; `device_replay=False` / `--host_replay` keep the
-reference's host sampling."""
+reference's host sampling.  `device_relabel=True` / `--device_relabel` (off by default) also mirrors the poses and forms the
+hindsight goals of a self-supervised on-policy buffer on the GPU (DeviceReplay(relabel="device")) instead of in a host loop."""
 import argparse
 import itertools
 import os
@@ -58,34 +59,42 @@ def device_replay_fits(memory, reserve=0.5):
     return need < reserve * free
 
 
-def device_mirror(memory):
+def device_mirror(memory, relabel="host"):
     """the HBM mirror of `memory`, built ONCE per memory object and kept on it (a caller that alternates
     train_off_policy with buffer writes must neither re-allocate GBs per call nor train on a stale snapshot): a later call
     uploads what was written in between -- DeviceReplay.sync_writes(): the clouds of the slots push() wrote, everything up to
-    upper_idx() when the buffer changed in any other way."""
+    upper_idx() when the buffer changed in any other way.  relabel: DeviceReplay's hindsight-goal mode; a mirror of each mode
+    is kept under its own name (a caller that uses both on one memory pays for both); a buffer named "expert" never relabels,
+    so its one mirror serves both modes."""
     from .device_replay import DeviceReplay
-    dmem = getattr(memory, "_gad_device_mirror", None)
+    if getattr(memory, "name", "") == "expert":
+        relabel = "host"
+    attr = "_gad_device_mirror" if relabel == "host" else "_gad_device_mirror_" + str(relabel)
+    dmem = getattr(memory, attr, None)
     if dmem is None or dmem.cap != memory.point_state.shape[0]:
-        dmem = DeviceReplay(memory)
-        memory._gad_device_mirror = dmem
+        dmem = DeviceReplay(memory, relabel=relabel)
+        setattr(memory, attr, dmem)
     else:
         dmem.sync_writes()
     return dmem
 
 
-def mixed_device_mirror(memory, online_memory, n_expert, n_online):
-    """device_mirror() of both buffers + ONE MixedDeviceReplay for the pair and the split, kept on the expert memory"""
+def mixed_device_mirror(memory, online_memory, n_expert, n_online, relabel="host"):
+    """device_mirror() of both buffers + ONE MixedDeviceReplay for the pair of mirrors and the split, kept on the expert memory
+    (the last four pairings: a caller that alternates online buffers or relabel modes re-allocates no staging sets)"""
     from .device_replay import MixedDeviceReplay
-    d0, d1 = device_mirror(memory), device_mirror(online_memory)
-    ent = getattr(memory, "_gad_mixed_mirror", None)
-    if ent is None or ent[0] is not d0 or ent[1] is not d1 or ent[2:4] != (int(n_expert), int(n_online)):
-        ent = (d0, d1, int(n_expert), int(n_online), MixedDeviceReplay([(d0, n_expert), (d1, n_online)]))
-        memory._gad_mixed_mirror = ent
+    d0, d1 = device_mirror(memory, relabel), device_mirror(online_memory, relabel)
+    kept = getattr(memory, "_gad_mixed_mirror", None) or []
+    for ent in kept:
+        if ent[0] is d0 and ent[1] is d1 and ent[2:4] == (int(n_expert), int(n_online)):
+            return ent[4]
+    ent = (d0, d1, int(n_expert), int(n_online), MixedDeviceReplay([(d0, n_expert), (d1, n_online)]))
+    memory._gad_mixed_mirror = [ent] + list(kept)[:3]
     return ent[4]
 
 
 def train_off_policy(agent, memory, config, model_output_dir=None, save_model=False, log=None, max_epochs=None,
-                     sample=None, run_ahead=False, device_replay="auto", rng=None, online_memory=None):
+                     sample=None, run_ahead=False, device_replay="auto", rng=None, online_memory=None, device_relabel=False):
     """The reference's train_off_policy() (:107-161) over an agent and a filled replay memory.
     config = cfg.RL_TRAIN (updates_per_step, batch_size, save_epoch, max_epoch).  `sample(batch_size)` overrides
     memory.sample (device-resident replay, prefetching samplers).  Returns the per-key loss history (deques, as the
@@ -97,28 +106,40 @@ def train_off_policy(agent, memory, config, model_output_dir=None, save_model=Fa
     online_memory: a second BaseMemory.  With config.onpolicy and n_on = int(batch_size * online_buffer_ratio) > 0 every
     update trains on batch_size rows of `memory` followed by n_on rows of `online_memory` (the reference learner's batch,
     core/trainer.py:212-232); the indices are drawn expert first.  Both buffers are mirrored in HBM under the same
-    `device_replay` rule (one gather launch per minibatch), else the host forms the batch (replay_memory.sample_mixed)."""
+    `device_replay` rule (one gather launch per minibatch), else the host forms the batch (replay_memory.sample_mixed).
+    device_relabel: the mirrors are built with relabel="device": the hindsight goals of a buffer that relabels (self_supervision,
+    not named "expert") are formed by one small launch behind the gather instead of BaseMemory.onpolicy_goals' host loop; equal
+    to the host's goals to float32 rounding, not bit for bit.  No effect on the host sampling path."""
+    relabel = "device" if device_relabel else "host"
+
+    def relabel_note(*mems):
+        """what the "mirrored in HBM" line says about hindsight goals when a buffer forms them"""
+        if not any(bool(getattr(m, "self_supervision", False)) and getattr(m, "name", "") != "expert" for m in mems):
+            return ""
+        return "; hindsight goals formed on the %s" % ("device (gad_replay_relabel_goals)" if device_relabel else
+                                                       "host (BaseMemory.onpolicy_goals); device_relabel=True forms them on the GPU")
     losses = get_loss_info_dict()
     n_on = int(config.batch_size * config.online_buffer_ratio) if (online_memory is not None and config.onpolicy) else 0
     total_batch = int(config.batch_size) + n_on
     if n_on > 0 and sample is None:
         if device_replay and hasattr(agent, "runtime") and (
                 device_replay is True or (device_replay_fits(memory) and device_replay_fits(online_memory))):
-            mixed = mixed_device_mirror(memory, online_memory, config.batch_size, n_on)
+            mixed = mixed_device_mirror(memory, online_memory, config.batch_size, n_on, relabel)
             sample = lambda batch_size: mixed.sample_lazy(rng=rng)                  # noqa: E731
             if log is not None:
                 log("replay buffers mirrored in HBM (%d expert + %d online transitions); device_replay=False keeps the host "
-                    "sampling path" % (len(memory), len(online_memory)))
+                    "sampling path%s" % (len(memory), len(online_memory), relabel_note(memory, online_memory)))
         else:
             sample = lambda batch_size: sample_mixed((memory, online_memory), (batch_size, n_on), rng=rng)   # noqa: E731
     if sample is None and device_replay and (device_replay is True or device_replay_fits(memory)) and hasattr(agent, "runtime"):
         # default feeding path (VERDICT r03 item 8): the buffer mirrored in HBM, indices drawn on the host with the
         # reference's arithmetic and random stream (np.random, as memory.sample uses), ONE gather launch per minibatch --
         # the only feeding path that keeps up with a 3 ms update step (bench.py: value_device_replay vs value_host_inclusive)
-        dmem = device_mirror(memory)
+        dmem = device_mirror(memory, relabel)
         sample = lambda batch_size: dmem.sample_lazy(batch_size, rng=rng)        # noqa: E731
         if log is not None:
-            log("replay buffer mirrored in HBM (%d transitions); device_replay=False keeps the host sampling path" % len(memory))
+            log("replay buffer mirrored in HBM (%d transitions); device_replay=False keeps the host sampling path%s"
+                % (len(memory), relabel_note(memory)))
     sample = sample or memory.sample
     epochs = 0
     # The loop below is the reference's: sample, update, read the losses -- every iteration.  What keeps the GPU busy across that
@@ -196,6 +217,9 @@ def main(argv=None):
     ap.add_argument("--max_epoch", type=int, default=None, help="overrides RL_TRAIN.max_epoch (update steps)")
     ap.add_argument("--host_replay", action="store_true", help="sample on the host and upload every minibatch (the reference's "
                                                                "loop); default: mirror the buffer in HBM when it fits")
+    ap.add_argument("--device_relabel", action="store_true", help="form the hindsight goals of a self-supervised on-policy buffer "
+                                                                  "on the GPU from mirrored poses (float32 closed form) instead "
+                                                                  "of in the host's per-row loop; default: the host forms them")
     args = ap.parse_args(argv)
     agent, cfg = setup(args.config_file, args.policy, args.pretrained, args.model_surfix, args.batch_size, args.output_dir)
     config = cfg.RL_TRAIN
@@ -213,7 +237,8 @@ def main(argv=None):
         online = BaseMemory(int(cfg.OFFLINE_RL_MEMORY_SIZE) + 1, config, name="online")
         online.load(args.online_data, int(cfg.OFFLINE_RL_MEMORY_SIZE))
     losses, epochs = train_off_policy(agent, memory, config, args.output_dir, args.save_model, log=print,
-                                      device_replay=False if args.host_replay else "auto", online_memory=online)
+                                      device_replay=False if args.host_replay else "auto", online_memory=online,
+                                      device_relabel=args.device_relabel)
     if args.save_model:
         agent.save_model(agent.update_step, output_dir=args.output_dir)
     return losses, epochs

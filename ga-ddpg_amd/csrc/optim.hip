@@ -524,6 +524,93 @@ extern "C" int gad_replay_gather_multi(const gad_replay_mix_args* a, void* strea
     return GAD_OK;
 }
 
+// Hindsight goals on the device (include/gaddpg.h section F): one lane per output row, after the gather that wrote out_goal.
+// A lane of a relabelling source whose row is on-policy (expert flag 0) reads the top three rows of its own pose A and of its
+// episode's last pose E (2 x 48 B; WIDE: three 16-byte loads each), forms R = A_R^T E_R, t = A_R^T (E_t - A_t) and the
+// quaternion of R by the closed form, and stores 7 floats; every other lane stores nothing.
+template <bool WIDE>
+__device__ __forceinline__ void load_pose_rows(const float* __restrict__ p, float (&m)[12]) {
+    if constexpr (WIDE) {
+        const float4* q = reinterpret_cast<const float4*>(p);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const float4 v = q[r];
+            m[4 * r] = v.x; m[4 * r + 1] = v.y; m[4 * r + 2] = v.z; m[4 * r + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) m[k] = p[k];
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(64) void replay_relabel_goals_kernel(gad_replay_relabel_args a) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.B) return;
+    const float* pose = nullptr;
+    const float* flags = nullptr;
+#pragma unroll
+    for (int k = 0; k < GAD_REPLAY_MAX_SRC; ++k)
+        if (k < a.n_src && b >= a.row_start[k] && b < a.row_start[k + 1]) { pose = a.src[k].state_pose; flags = a.src[k].expert_flags; }
+    if (!pose) return;                                   // this source keeps its stored goals
+    const long long i = a.idx[b];
+    if (flags[i] != 0.0f) return;                        // an expert row keeps its goal (a NaN flag too: NaN == 0 is false on the host)
+    const long long e = a.end[b];
+    float A[12], E[12];
+    load_pose_rows<WIDE>(pose + (size_t)i * 16, A);
+    load_pose_rows<WIDE>(pose + (size_t)e * 16, E);
+    float R[3][3], t[3];
+    const float d0 = E[3] - A[3], d1 = E[7] - A[7], d2 = E[11] - A[11];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R[r][c] = A[r] * E[c] + A[4 + r] * E[4 + c] + A[8 + r] * E[8 + c];
+        t[r] = A[r] * d0 + A[4 + r] * d1 + A[8 + r] * d2;
+    }
+    // the four candidates 4w^2, 4x^2, 4y^2, 4z^2 (they sum to 4, so the largest is >= 1 for any finite R) and the component
+    // vector (4 w q, 4 x q, 4 y q or 4 z q) of the branch the largest one picks
+    const float cw = 1.f + R[0][0] + R[1][1] + R[2][2], cx = 1.f + R[0][0] - R[1][1] - R[2][2];
+    const float cy = 1.f - R[0][0] + R[1][1] - R[2][2], cz = 1.f - R[0][0] - R[1][1] + R[2][2];
+    float m = cw, q0 = cw, q1 = R[2][1] - R[1][2], q2 = R[0][2] - R[2][0], q3 = R[1][0] - R[0][1];
+    if (cx > m) { m = cx; q0 = R[2][1] - R[1][2]; q1 = cx; q2 = R[0][1] + R[1][0]; q3 = R[0][2] + R[2][0]; }
+    if (cy > m) { m = cy; q0 = R[0][2] - R[2][0]; q1 = R[0][1] + R[1][0]; q2 = cy; q3 = R[1][2] + R[2][1]; }
+    if (cz > m) { m = cz; q0 = R[1][0] - R[0][1]; q1 = R[0][2] + R[2][0]; q2 = R[1][2] + R[2][1]; q3 = cz; }
+    const float s = 0.5f / sqrtf(m);                     // 1 / (4 |largest component|)
+    q0 *= s; q1 *= s; q2 *= s; q3 *= s;
+    const float inv = 1.f / sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+    q0 *= inv; q1 *= inv; q2 *= inv; q3 *= inv;
+    if (q0 < 0.f) { q0 = -q0; q1 = -q1; q2 = -q2; q3 = -q3; }
+    if (!(isfinite(q0) && isfinite(q1) && isfinite(q2) && isfinite(q3))) { q0 = 1.f; q1 = q2 = q3 = 0.f; }
+    float* g = a.out_goal + (size_t)b * 7;
+    g[0] = q0; g[1] = q1; g[2] = q2; g[3] = q3; g[4] = t[0]; g[5] = t[1]; g[6] = t[2];
+}
+
+extern "C" int gad_replay_relabel_goals(const gad_replay_relabel_args* a, void* stream) {
+    GAD_REQUIRE(a, GAD_ERR_NULL, "replay_relabel_goals: null arguments");
+    GAD_REQUIRE(a->n_src >= 1 && a->n_src <= GAD_REPLAY_MAX_SRC, GAD_ERR_SHAPE, "replay_relabel_goals: n_src %d outside 1..%d",
+                a->n_src, GAD_REPLAY_MAX_SRC);
+    GAD_REQUIRE(a->B >= 1 && a->B <= 65535, GAD_ERR_SHAPE, "replay_relabel_goals: B %d outside 1..65535", a->B);
+    GAD_REQUIRE(a->row_start[0] == 0 && a->row_start[a->n_src] == a->B, GAD_ERR_SHAPE,
+                "replay_relabel_goals: row_start must run from 0 to B = %d, got %d .. %d", a->B, a->row_start[0], a->row_start[a->n_src]);
+    for (int s = 0; s < a->n_src; ++s)
+        GAD_REQUIRE(a->row_start[s + 1] >= a->row_start[s], GAD_ERR_SHAPE, "replay_relabel_goals: row_start decreases at source %d", s);
+    GAD_REQUIRE(a->idx && a->end, GAD_ERR_NULL, "replay_relabel_goals: null index vector");
+    GAD_REQUIRE(a->out_goal, GAD_ERR_NULL, "replay_relabel_goals: null output");
+    bool wide = true;
+    for (int s = 0; s < a->n_src; ++s) {
+        const gad_replay_relabel_src& S = a->src[s];
+        if (a->row_start[s + 1] == a->row_start[s] || !S.state_pose) continue;       // owns no row, or does not relabel: never read
+        GAD_REQUIRE(S.expert_flags, GAD_ERR_NULL, "replay_relabel_goals: null expert_flags in source %d", s);
+        wide = wide && (reinterpret_cast<size_t>(S.state_pose) & 15) == 0;
+    }
+    if (wide)
+        hipLaunchKernelGGL(replay_relabel_goals_kernel<true>, dim3(gad_cdiv(a->B, 64)), dim3(64), 0, (hipStream_t)stream, *a);
+    else
+        hipLaunchKernelGGL(replay_relabel_goals_kernel<false>, dim3(gad_cdiv(a->B, 64)), dim3(64), 0, (hipStream_t)stream, *a);
+    GAD_CHECK_LAUNCH("replay_relabel_goals");
+    return GAD_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // one launch clears up to six buffers (statistics, gradient arenas, scatter targets of a backward pass): each of
 // them used to be its own fill kernel at the head / in the middle of the pass's dependency chain

@@ -122,6 +122,7 @@ const std::vector<reg_entry>& registry() {
         GAD_PLAN_ENTRY(gad_split_weights)
         GAD_PLAN_ENTRY(gad_replay_gather)
         GAD_PLAN_ENTRY(gad_replay_gather_multi)
+        GAD_PLAN_ENTRY(gad_replay_relabel_goals)
         GAD_PLAN_ENTRY(gad_zero_buffers)
         GAD_PLAN_ENTRY(gad_copy_buffers)
         return v;

@@ -84,6 +84,15 @@ class ReplayMixArgs(C.Structure):
                 ("out_time_m1", _vp), ("out_expert_flag", _vp), ("out_perturb_flag", _vp)]
 
 
+class ReplayRelabelSrc(C.Structure):
+    _fields_ = [("state_pose", _vp), ("expert_flags", _vp)]
+
+
+class ReplayRelabelArgs(C.Structure):
+    _fields_ = [("B", _i32), ("n_src", _i32), ("row_start", _i32 * (REPLAY_MAX_SRC + 1)),
+                ("src", ReplayRelabelSrc * REPLAY_MAX_SRC), ("idx", _vp), ("end", _vp), ("out_goal", _vp)]
+
+
 class OptimJob(C.Structure):
     _fields_ = [("n", _i32), ("p", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("active", _vp), ("m2p", _vp),
                 ("packed", _vp), ("gacc", _vp), ("accumulate", _i32), ("hyper", _vp), ("clip_sumsq", _vp), ("clip_max", _f32),
@@ -135,7 +144,7 @@ def lib():
 
 
 EXPORTS = (
-    "gad_abi_version", "gad_last_kernel", "gad_last_error", "gad_set_option", "gad_timing_slot", "gad_stream_priority", "gad_wall_clock_khz", "gad_grid_rows_hint", "gad_bn_running_update", "gad_replay_gather", "gad_replay_gather_multi", "gad_zero_buffers", "gad_furthest_point_sampling", "gad_gather_points",
+    "gad_abi_version", "gad_last_kernel", "gad_last_error", "gad_set_option", "gad_timing_slot", "gad_stream_priority", "gad_wall_clock_khz", "gad_grid_rows_hint", "gad_bn_running_update", "gad_replay_gather", "gad_replay_gather_multi", "gad_replay_relabel_goals", "gad_zero_buffers", "gad_furthest_point_sampling", "gad_gather_points",
     "gad_gather_points_grad", "gad_ball_query", "gad_group_points", "gad_group_points_grad",
     "gad_query_and_group", "gad_prep_points", "gad_rows_from_ball_query", "gad_rows_group_all",
     "gad_gemm_fwd", "gad_bn_finalize", "gad_bn_eval_affine", "gad_segment_pool", "gad_pool_finalize", "gad_affine_act", "gad_transpose_batched",

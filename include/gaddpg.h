@@ -51,7 +51,7 @@ int gad_abi_version(void);                 /* bumped on any signature change or 
                                             * action_bias in gad_policy_outputs;
                                             * 12: the Adam `hyper` block is GAD_ADAM_HYPER = 10 floats (1 - beta1, 1 - beta2
                                             * appended); added under 12 without a bump (no existing signature or struct
-                                            * layout changed): gad_replay_gather_multi                                  */
+                                            * layout changed): gad_replay_gather_multi, gad_replay_relabel_goals        */
 /* diagnostics: which kernel family the last gad_gemm_fwd / _dx / _dw / _bwd call routed to ("gemm_fwd(stream)",
  * "gemm_dx(wide)", "gemm_bwd(stream)", "gemm_dw" = generic tile kernel, ...); bench.py labels its per-kernel table
  * with it instead of restating the routing rules.                                                  */
@@ -582,7 +582,8 @@ int gad_split_weights(const float* packed, const gad_split_layer* host_layers, i
  *    time[b] = timestep[end[b]] + 1 - timestep[idx[b]], time_m1 = time - 1.
  *    gad_replay_gather reads one buffer; gad_replay_gather_multi fills the same outputs from up to four buffers (the
  *    expert + online minibatch of the reference's learner), each block of output rows from its own source, and folds the
- *    hindsight-goal overwrite into the launch.
+ *    hindsight-goal overwrite into the launch (goals formed on the host); gad_replay_relabel_goals forms those goals on the
+ *    device instead, in a launch of its own behind either gather.
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t B;
@@ -638,6 +639,44 @@ typedef struct {
 } gad_replay_mix_args;
 
 int gad_replay_gather_multi(const gad_replay_mix_args* host_args, void* stream);
+
+/* Hindsight goals formed on the device (reference core/replay_memory.py:233-249: the goal of an on-policy row becomes the pose
+ * its own episode ended in, seen from the row's pose).  Runs on the gather's stream AFTER the gather that wrote out_goal and
+ * updates it in place.  B, n_src and row_start have gad_replay_gather_multi's meaning; idx[b] and end[b] are local to the
+ * source that owns row b.  A source whose state_pose is NULL does not relabel: its rows are left alone.  For row b of a
+ * relabelling source with expert_flags[idx[b]] == 0.0f:
+ *   A = state_pose[idx[b]], E = state_pose[end[b]]   (row-major 4 x 4; the bottom rows are taken as (0, 0, 0, 1) and not read)
+ *   R = A_R^T E_R, t = A_R^T (E_t - A_t)             (= se3_inverse(A) . E)
+ *   out_goal[b] = [quaternion (w, x, y, z) of R | t]
+ * Every other row of out_goal is not written at all.  The quaternion is the float32 closed form: of the four candidates
+ * 1 + tr, 1 + R00 - R11 - R22, 1 - R00 + R11 - R22, 1 - R00 - R11 + R22 (= 4w^2, 4x^2, 4y^2, 4z^2) the largest, m, picks the
+ * branch; its component vector is divided by 2 sqrt(m), normalised to unit length and negated if w < 0.  If any component
+ * comes out non-finite the identity quaternion (1, 0, 0, 0) is written ("identity when the conversion fails", reference
+ * core/utils.py:299-306; the host's own answer for NaN input depends on LAPACK and is not reproduced); t is written as
+ * computed.
+ * Contract: rigid poses, i.e. R orthonormal to float32 rounding; the result then agrees with the host's
+ * BaseMemory.onpolicy_goals to float32 rounding of the 3 x 3 products (not bit for bit: tests/test_gpu_device_relabel.py
+ * states the gate).  For any other finite matrix the output is finite and of unit length but is NOT the host's Bar-Itzhack
+ * best fit (a zero matrix gives (1, 0, 0, 0) here, (0, 1, 0, 0) on the host).
+ * One lane per row, 64-lane workgroups; pose rows are read as 16-byte groups when every relabelling source's state_pose is
+ * 16-byte aligned, as single floats otherwise (same result either way).
+ * Refused before any launch: NULL args (GAD_ERR_NULL); n_src outside 1..GAD_REPLAY_MAX_SRC, B outside 1..65535, a row_start
+ * that does not run 0 .. B without decreasing (GAD_ERR_SHAPE); NULL idx, end or out_goal, a source that owns rows and has
+ * state_pose set but expert_flags NULL (GAD_ERR_NULL). */
+typedef struct {
+    const float* state_pose;             /* (cap, 16) row-major 4 x 4 poses, or NULL: this source's rows keep their goals */
+    const float* expert_flags;           /* (cap) */
+} gad_replay_relabel_src;
+typedef struct {
+    int32_t B;
+    int32_t n_src;
+    int32_t row_start[GAD_REPLAY_MAX_SRC + 1];
+    gad_replay_relabel_src src[GAD_REPLAY_MAX_SRC];
+    const int64_t* idx; const int64_t* end;                               /* (B) device index vectors, source-local */
+    float* out_goal;                     /* (B, 7), updated in place */
+} gad_replay_relabel_args;
+
+int gad_replay_relabel_goals(const gad_replay_relabel_args* host_args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * G. housekeeping
