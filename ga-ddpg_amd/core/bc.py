@@ -19,11 +19,14 @@ class BC(Agent):
         return [self.policy.state_dict(), self.goal_feature_extractor.state_dict(),
                 self.state_feature_extractor.state_dict()]
 
-    def update_parameters(self, batch_data, updates, k):
+    def update_parameters(self, batch_data, updates, k, sync=True):
+        """One gradient step.  sync=False: return as soon as the step is enqueued -- the result dict fills in on first read
+        (PendingLog), the host goes on to sample / stage / enqueue the next step while this one runs, up to
+        engine.HOST_RING - 1 steps ahead (agent.flush() waits for all)."""
         self.set_mode(False)
         ps = batch_data["point_state_batch"]
         rt = self.runtime(ps.shape[0], ps.shape[2])
-        s = rt.bc_step(batch_data)
+        s = rt.bc_step(batch_data, sync=sync)
         self.update_step += 1
         self.pi, self.aux_pred = rt.pi, rt.aux_pred
-        return self._result(s, False)
+        return self._result(s, False) if sync else self._pending_result(s, False)

@@ -14,6 +14,7 @@ gather launch instead of a 17 MB host gather + PCIe upload per step; `device_rep
 reference's host sampling.  `device_relabel=True` / `--device_relabel` (off by default) also mirrors the poses and forms the
 hindsight goals of a self-supervised on-policy buffer on the GPU (DeviceReplay(relabel="device")) instead of in a host loop."""
 import argparse
+import inspect
 import itertools
 import os
 import time
@@ -110,6 +111,9 @@ def train_off_policy(agent, memory, config, model_output_dir=None, save_model=Fa
     device_relabel: the mirrors are built with relabel="device": the hindsight goals of a buffer that relabels (self_supervision,
     not named "expert") are formed by one small launch behind the gather instead of BaseMemory.onpolicy_goals' host loop; equal
     to the host's goals to float32 rounding, not bit for bit.  No effect on the host sampling path."""
+    if run_ahead and "sync" not in inspect.signature(agent.update_parameters).parameters:
+        raise TypeError("train_off_policy(run_ahead=True): %s.update_parameters takes no `sync` argument, its updates cannot be "
+                        "enqueued without waiting for each" % type(agent).__name__)
     relabel = "device" if device_relabel else "host"
 
     def relabel_note(*mems):
@@ -165,7 +169,7 @@ def train_off_policy(agent, memory, config, model_output_dir=None, save_model=Fa
                 agent.prefetch(ahead)
             data_time += time.time() - start_time
             start_time = time.time()
-            if run_ahead and "sync" in agent.update_parameters.__code__.co_varnames:
+            if run_ahead:
                 pending.append(agent.update_parameters(batch_data, agent.update_step, i, sync=False))
             else:
                 pending.append(agent.update_parameters(batch_data, agent.update_step, i))

@@ -28,6 +28,10 @@ EARLY_ZERO = _os.environ.get("GAD_EARLY_ZERO", "1") == "1"   # backward buffers 
 INPUT_SETS = int(_os.environ.get("GAD_INPUT_SETS", "2"))      # 1: uploads + geometry in front of every step (round-1 schedule)
 STEP_PLAN = _os.environ.get("GAD_STEP_PLAN", "1") == "1"      # the whole update step as ONE replayed launch list (FusedRuntime._step_plan);
                                                               # 0: enqueued call by call from Python (_ddpg_enqueue: the same launches)
+# BC only, A/B: prefetch_inputs() enqueues the staging at once (into the set the step after the coming one uses) instead of behind
+# the coming step's launches.  OFF: measured +1 - 3 % over no prefetch where the deferred order gives +12 %
+# (profiles/bc_pipeline.txt), and it only pays for a caller that hints before it updates
+BC_PREFETCH_EARLY = _os.environ.get("GAD_BC_PREFETCH_EARLY", "0") == "1"
 
 
 def _dev_f32(x, dev):
@@ -47,7 +51,7 @@ def _fold_stats(s, fused):
 
 
 class PendingStep(object):
-    """result block of a step that was enqueued without waiting for it (ddpg_step(sync=False)); wait() blocks until the
+    """result block of a step that was enqueued without waiting for it (ddpg_step / bc_step(sync=False)); wait() blocks until the
     step has run and returns a private copy of the 32 floats"""
 
     def __init__(self, event, view, fused=False):
@@ -129,11 +133,13 @@ class FusedRuntime(object):
         # backward pass instead of in front of step N+1's critical chain.  Activation scratch is shared (engine.slot_view).
         self._sets = [dict(dbuf=self.dbuf, geo=self.geo, geo_next=getattr(self, "geo_next", None), slot_p=self.slot_p,
                            slot_v=getattr(self, "slot_v", None), slot_t=getattr(self, "slot_t", None))]
-        if INPUT_SETS > 1 and self.has_critic:
-            geo2, geon2 = engine.Geometry(B, self.N, sa1, sa2, dev), engine.Geometry(B, self.N, sa1, sa2, dev)
+        if INPUT_SETS > 1:
+            geo2 = engine.Geometry(B, self.N, sa1, sa2, dev)
+            geon2 = engine.Geometry(B, self.N, sa1, sa2, dev) if self.has_critic else None      # (a BC step has no next-state pass)
             self._sets.append(dict(dbuf={k: torch.zeros_like(v) for k, v in self.dbuf.items()}, geo=geo2, geo_next=geon2,
-                                   slot_p=engine.slot_view(self.slot_p, geo2), slot_v=engine.slot_view(self.slot_v, geo2),
-                                   slot_t=engine.slot_view(self.slot_t, geon2)))
+                                   slot_p=engine.slot_view(self.slot_p, geo2),
+                                   slot_v=engine.slot_view(self.slot_v, geo2) if self.has_critic else None,
+                                   slot_t=engine.slot_view(self.slot_t, geon2) if self.has_critic else None))
         for st in self._sets:
             st["rows_pin"] = torch.zeros(4, dtype=torch.int32).pin_memory()    # live rows of [geo SA1, SA2, geo_next SA1, SA2]
             st.update(ev_in=torch.cuda.Event(), ev_gn=torch.cuda.Event(), ev_g=torch.cuda.Event(), ev_up=torch.cuda.Event(), ev_free=None,
@@ -159,7 +165,7 @@ class FusedRuntime(object):
         # One launch per optimiser phase (gad_optim_jobs: arena -> .grad, Adam, target update, log statistics, BatchNorm
         # counters) instead of ~6 / ~12 small ones; a data-parallel run exchanges gradients between the conversion and the
         # Adam step: the backward plans then convert arena -> .grad themselves and the launch starts from .grad.
-        self.fused_optim = self.has_critic and _os.environ.get("GAD_FUSED_OPTIM", "1") == "1"
+        self.fused_optim = _os.environ.get("GAD_FUSED_OPTIM", "1") == "1"
         # this step's Adam scalars of every network: one pinned block per in-flight step, ONE upload
         self._opt_nets = [self.pol, self.enc] + ([self.venc, self.cr] if self.has_critic else [])
         self.hyper_all = torch.zeros(len(self._opt_nets), engine.ADAM_HYPER, **f32)
@@ -184,7 +190,7 @@ class FusedRuntime(object):
     def set_fused_optim(self, on):
         """switch between one optimiser launch per phase and the separate conversion / Adam / target / statistics launches
         (rebuilds the backward plans: the fused launch takes over their arena -> .grad tail)"""
-        on = bool(on) and self.has_critic
+        on = bool(on)
         if on != self.fused_optim:
             self.fused_optim = on
             self._build_all_plans()
@@ -199,7 +205,7 @@ class FusedRuntime(object):
     def _grad_tail(self, plan, head, enc, tag, early):
         """arena (f64, packed) -> flat .grad (f32, master order) at the end of a backward plan; bucketed: only what the
         early hook has not converted yet (the encoder's SA1 parameters, which lead its flat buffer)"""
-        if self.fused_optim and self.has_critic and self.dp is None:
+        if self.fused_optim and self.dp is None:
             # the optimiser launch converts (gad_optim_jobs); only the critic's gradient is needed before it: clip_grad_norm_
             # (data-parallel runs convert here instead: the exchange sits between the conversion and the optimiser launch)
             if tag == "c":             # ... with the sum of squares of the result in the same launch (self.clip_sumsq is cleared with
@@ -321,7 +327,7 @@ class FusedRuntime(object):
         the static buffers (gad_copy_buffers; "time minus one" formed on the way), no host traffic.  `keys`: only these
         (staged upload)."""
         import ctypes as C
-        ks = [k for k in (BATCH_KEYS if keys is None else keys) if k in dbatch]
+        ks = [k for k in (BATCH_KEYS if keys is None else keys) if k in dbatch and (self.has_critic or k != "next_point_state_batch")]
         segs = []
         for k in ks:
             src, dst = dbatch[k], self.dbuf[k]
@@ -347,7 +353,9 @@ class FusedRuntime(object):
         if "replay_gather" in batch:             # DeviceReplay.sample_lazy(): one gather launch into the static buffers
             if int(batch["idx"].shape[0]) != self.B:
                 raise RuntimeError("batch size changed: runtime was built for B=%d" % self.B)
-            return batch["replay_gather"].gather_into(batch, self.dbuf)
+            # (a BC step reads no next-state cloud: a NULL destination makes the gather kernels skip that half)
+            return batch["replay_gather"].gather_into(batch, self.dbuf if self.has_critic else
+                                                      dict(self.dbuf, next_point_state_batch=None))
         if torch.is_tensor(batch["point_state_batch"]):
             return self.load_device_batch(batch, keys)
         B = self.B
@@ -397,15 +405,19 @@ class FusedRuntime(object):
             self._jobs_gen = getattr(self, "_jobs_gen", 0) + 1
             jobs = self._optim_jobs_cache = {
                 "key": (id(self.pol.flat.grad), id(self.enc.flat.grad), bool(ag.train_feature), ar),
-                # value encoder: arena -> grad + Adam; critic: Adam with the clip (its .grad is converted already) + target
-                # update from the updated parameters (nothing reads critic_target before the next step) + max |parameter|
-                "c": arr([self._optim_job(self.venc.flat, arena=ar),
-                          self._optim_job(self.cr.flat, arena=False, clip=self.clip_sumsq, target=self.cr_t.flat, sel=self.critic_sel,
-                                          absmax_p=engine._ptr(sc, 48))]),
+                # policy: arena -> grad + Adam + target update + max |parameter|; policy encoder: arena -> grad + Adam (when it
+                # trains) + its BatchNorm counters.  This is the whole optimiser phase of a BC step
                 "a": arr([self._optim_job(self.pol.flat, arena=ar, target=self.pol_t.flat, absmax_p=engine._ptr(sc, 32)),
-                          self._optim_job(self.enc.flat, arena=ar, adam=bool(ag.train_feature), counter=self.enc.batches_tracked)]),
-                "end": arr([self._optim_job(self.cr.flat, adam=False, arena=False, absmax_grad=engine._ptr(sc, 40),
-                                            counter=self.venc.batches_tracked)])}
+                          self._optim_job(self.enc.flat, arena=ar, adam=bool(ag.train_feature), counter=self.enc.batches_tracked)])}
+            if not self.has_critic:
+                return jobs
+            # value encoder: arena -> grad + Adam; critic: Adam with the clip (its .grad is converted already) + target
+            # update from the updated parameters (nothing reads critic_target before the next step) + max |parameter|
+            jobs["c"] = arr([self._optim_job(self.venc.flat, arena=ar),
+                             self._optim_job(self.cr.flat, arena=False, clip=self.clip_sumsq, target=self.cr_t.flat, sel=self.critic_sel,
+                                             absmax_p=engine._ptr(sc, 48))])
+            jobs["end"] = arr([self._optim_job(self.cr.flat, adam=False, arena=False, absmax_grad=engine._ptr(sc, 40),
+                                               counter=self.venc.batches_tracked)])
             # the end-of-step bookkeeping (max |critic.grad| as the reference logs it after the actor backward, the value encoder's
             # BatchNorm counters) folded into a launch that runs anyway -- one dependent launch fewer at the step boundary:
             #   policy steps: a third job of the actor phase's launch (critic.grad is final once the actor-critic backward added to it);
@@ -436,7 +448,7 @@ class FusedRuntime(object):
         else:
             js = jobs["a+end"] if (fold and policy_step) else jobs["a"]
             js[0].tau = float(ag.tau)
-            js[1].counter_add = 0 if ev else 2
+            js[1].counter_add = 0 if ev else (2 if self.has_critic else 1)      # policy-encoder passes of the step: DDPG two, BC one
             if len(js) == 3:
                 js[2].counter_add = 0 if ev else 3
         return js
@@ -525,13 +537,14 @@ class FusedRuntime(object):
                     if st["geo_next"] is not None:
                         st["geo_next"].rows_hint[stage] = h
 
-    def _end_step(self, slot, sync):
+    def _end_step(self, slot, sync, fused=None):
+        """fused: the step's optimiser phases ran as gad_optim_jobs launches (default: self.fused_optim)"""
         ev = self._ev_done[slot]
         if ev is None:
             ev = self._ev_done[slot] = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         self._sets[self._set]["ev_free"] = ev        # every stream of the step has been joined into this one by now
-        fused = self.fused_optim and self.has_critic
+        fused = self.fused_optim if fused is None else fused
         if sync:
             ev.synchronize()
             return _fold_stats(self.scal_host.numpy(), fused)
@@ -545,6 +558,27 @@ class FusedRuntime(object):
                 p.wait()
         torch.cuda.current_stream().synchronize()
 
+    def _replays(self):
+        """True: the update step runs as ONE replayed launch list (_step_plan); False: enqueued call by call from Python"""
+        if self.has_critic:
+            return STEP_PLAN and OVERLAP_PASSES and self.fused_optim
+        # BC: one stream of launches anyway; a data-parallel BC run and the one-stream diagnostic keep the call-by-call enqueue
+        return STEP_PLAN and self.fused_optim and self.dp is None and not engine.SERIAL
+
+    def _finish_step(self, slot, sync, replay, fused=None):
+        """close a step; a minibatch handed to prefetch_inputs() meanwhile is staged behind the step's own launches, before the
+        host waits for its result"""
+        nxt, self._next_batch = getattr(self, "_next_batch", None), None
+        if nxt is not None and replay:
+            pend = self._end_step(slot, False, fused)
+            self._prefetch_now(nxt)
+            if not sync:
+                return pend
+            v = pend.wait()
+            self._pending[slot] = None
+            return v
+        return self._end_step(slot, sync, fused)
+
     def ddpg_step(self, batch, noise_u=None, sync=True, test=False):
         """one DDPG / TD3 update: eager multi-stream enqueue.
         sync=False: return a PendingStep right after the enqueue.  The host then prepares and enqueues the next step while
@@ -554,7 +588,7 @@ class FusedRuntime(object):
         policy_step = ag.update_step % ag.policy_update_gap == 0
         slot = self._begin_step(alternate=True)
         self._eval = bool(test)
-        replay = (not test) and STEP_PLAN and OVERLAP_PASSES and self.fused_optim and self.has_critic
+        replay = (not test) and self._replays()
         if not replay:
             self._sets[self._set]["prefetched"] = None        # (the call-by-call path stages its inputs itself)
         if test:
@@ -570,16 +604,7 @@ class FusedRuntime(object):
             self._ddpg_replay(batch, noise_u, policy_step)
         else:
             self._ddpg_enqueue(batch, noise_u, policy_step)
-        nxt, self._next_batch = getattr(self, "_next_batch", None), None
-        if nxt is not None and replay:
-            pend = self._end_step(slot, sync=False)
-            self._prefetch_now(nxt)               # (after the step's own launches, before the host waits for its result)
-            if not sync:
-                return pend
-            v = pend.wait()
-            self._pending[slot] = None
-            return v
-        return self._end_step(slot, sync)
+        return self._finish_step(slot, sync, replay)
 
     # ------------------------------------------------------------------ the step as ONE replayed launch list
     def _step_key(self):
@@ -613,43 +638,53 @@ class FusedRuntime(object):
         cache[(set_index, policy_step)] = ent
         return ent
 
-    def _build_step_plan(self, st, policy_step):
-        ag, d, P = self.agent, self.dbuf, self.plans
-        B = self.B
+    def _prefetch_plan(self, st):
+        """The prefetch lanes of input / geometry set `st` (the bound one) as a list of its own, ONE per set: [geometry of the next
+        state] and [geometry of the current state] -- a BC runtime has only the latter; the uploads were enqueued on these
+        streams by the prelude (_stage_inputs).  Every kind of step starts from its events; prefetch_inputs() replays it for the
+        NEXT step's minibatch while the current step runs."""
+        d = self.dbuf
         EH = engine.EventHolder
+        PRE, PRE2 = 20, 21
         if "ev_up_h" not in st:
             st["ev_up_h"] = EH()
             st["ev_up"] = st["ev_up_h"].event
             st["geo_plan"] = self.geo.plan(d["point_state_batch"])
-            st["geo_next_plan"] = self.geo_next.plan(d["next_point_state_batch"])
-        H = {}                                  # items patched per step
-        MAIN, S1, S2, SC, PRE, PRE2 = 0, 1, 2, 3, 20, 21
-        # ---- prefetch lanes: [geometry of the next state] and [geometry of the current state]; the uploads were enqueued on
-        # these streams by the prelude (_stage_inputs).  This part is a list of its own, ONE per input set (both kinds of step
-        # start from its events): prefetch_inputs() replays it for the NEXT step's minibatch while the current step runs
+            st["geo_next_plan"] = self.geo_next.plan(d["next_point_state_batch"]) if self.has_critic else None
         cache = self.__dict__["_step_plans"]
         pre = cache.get(("pre", self._set))
         if pre is None:
             ev_in, ev_gn, ev_g = EH(), EH(), EH()
             M = Plan()
             M.keep.append((ev_in, ev_gn, ev_g, st["ev_up_h"]))
-            M.record(ev_in, on=PRE)
-            M.extend(st["geo_next_plan"], on=PRE)
-            M.record(ev_gn, on=PRE)
-            if ROW_HINTS:
-                M.memcpy(st["rows_pin"].data_ptr() + 8, self.geo_next.rows_n.data_ptr(), 8, on=PRE)
-            M.wait_event(ev_in, on=PRE2)
+            if self.has_critic:
+                M.record(ev_in, on=PRE)
+                M.extend(st["geo_next_plan"], on=PRE)
+                M.record(ev_gn, on=PRE)
+                if ROW_HINTS:
+                    M.memcpy(st["rows_pin"].data_ptr() + 8, self.geo_next.rows_n.data_ptr(), 8, on=PRE)
+                M.wait_event(ev_in, on=PRE2)
             M.record(st["ev_up_h"], on=PRE2)                    # every input of the step has left the caller's buffers
             M.extend(st["geo_plan"], on=PRE2)
             M.record(ev_g, on=PRE2)
-            if ROW_HINTS:
+            if ROW_HINTS and self.has_critic:
                 M.memcpy(st["rows_pin"].data_ptr(), self.geo.rows_n.data_ptr(), 8, on=PRE2)
             pre = cache[("pre", self._set)] = dict(plan=M, ev_gn=ev_gn, ev_g=ev_g)
+        return pre
+
+    def _build_step_plan(self, st, policy_step):
+        ag, d, P = self.agent, self.dbuf, self.plans
+        B = self.B
+        EH = engine.EventHolder
+        H = {}                                  # items patched per step
+        MAIN, S1, S2, SC = 0, 1, 2, 3
+        pre = self._prefetch_plan(st)
         Mpre, ev_gn, ev_g = pre["plan"], pre["ev_gn"], pre["ev_g"]
-        M = Mstep = Plan()
+        M = Plan()
         ev0, ev1, ev2, ev3, ev4, ev_run, ev_counts = (EH() for _ in range(7))
         M.keep.append((ev0, ev1, ev2, ev3, ev4, ev_run, ev_counts, pre))
-        M = Mstep
+        if not self.has_critic:
+            return self._build_bc_plan(M, H, Mpre, ev_g)
         # ---- critic phase (the comments of _ddpg_enqueue apply line by line)
         M.record(ev0, on=MAIN)
         M.wait_event(ev_gn, on=MAIN)
@@ -670,30 +705,16 @@ class FusedRuntime(object):
         M.extend(P["t2"], on=MAIN)
 
         def actor_tail(g_pi, on):
-            H["actor_loss"] = M.call("gad_actor_loss", self.hs_p.out, self.pi, d["expert_action_batch"], d["expert_flag_batch"],
-                                     d["return_batch"], d["goal_batch"], B, self.pol.n_heads, 0.0, int(bool(ag.policy_aux)),
-                                     self.action_scale, g_pi, self.inv_n_actor(), self.hs_p.g_out, engine._ptr(self.scal, 4), on=on)
-            M.extend(P["p_bwd"], on=on)
-            if self.allreduce is not None:
-                M.fn(lambda: self._reduce([self.pol.flat, self.enc.flat], "a"), on=on)
-            optim("a", on)
+            self._plan_actor_tail(M, H, policy_step, g_pi, on)
 
         def optim(which, on):
-            js = self._optim_select(which, policy_step)
-            if js is None:
-                return
-            M.call("gad_optim_jobs", js, len(js), on=on)
-            fl = self.venc.flat if which == "c" else (self.enc.flat if (which == "a" and ag.train_feature) else None)
-            if fl is not None and fl.split is not None:
-                M.call("gad_split_weights", fl.packed, fl._split_layers, len(fl._split_layers), fl.split, on=on)
+            self._plan_optim(M, policy_step, which, on)
 
         M.wait_event(ev2, on=S2)
         M.wait_event(ev0, on=S2)
         M.wait_event(ev_g, on=S2)
         M.extend(P["p_fwd"], on=S2)
-        nh = self.pol.n_heads
-        M.call("gad_policy_outputs", self.hs_p.out, B, nh, self.action_scale, self.action_bias, self.pi, self.aux_pred if nh == 13 else None,
-               on=S2)
+        self._plan_policy_outputs(M, S2)
         if not policy_step:
             actor_tail(None, S2)
         M.record(ev1, on=S1)
@@ -728,12 +749,55 @@ class FusedRuntime(object):
         H["download"] = M.memcpy(self._scal_ring[0].data_ptr(), self.scal.data_ptr(), 4 * self.scal.numel(), on=MAIN)
         return dict(plan=M, pre=Mpre, items=H, last={})
 
+    def _plan_policy_outputs(self, M, on):
+        nh = self.pol.n_heads
+        M.call("gad_policy_outputs", self.hs_p.out, self.B, nh, self.action_scale, self.action_bias, self.pi,
+               self.aux_pred if nh == 13 else None, on=on)
+
+    def _plan_actor_tail(self, M, H, policy_step, g_pi, on, coef=0.0):
+        """behaviour-cloning loss (its coefficient `coef` is patched per step by the DDPG step: 1 - mix ratio) -> policy backward ->
+        the actor phase's optimiser launch"""
+        ag, d = self.agent, self.dbuf
+        H["actor_loss"] = M.call("gad_actor_loss", self.hs_p.out, self.pi, d["expert_action_batch"], d["expert_flag_batch"],
+                                 d["return_batch"], d["goal_batch"], self.B, self.pol.n_heads, coef, int(bool(ag.policy_aux)),
+                                 self.action_scale, g_pi, self.inv_n_actor(), self.hs_p.g_out, engine._ptr(self.scal, 4), on=on)
+        M.extend(self.plans["p_bwd"], on=on)
+        if self.allreduce is not None:
+            M.fn(lambda: self._reduce([self.pol.flat, self.enc.flat], "a"), on=on)
+        self._plan_optim(M, policy_step, "a", on)
+
+    def _plan_optim(self, M, policy_step, which, on):
+        js = self._optim_select(which, policy_step)
+        if js is None:
+            return
+        M.call("gad_optim_jobs", js, len(js), on=on)
+        fl = self.venc.flat if which == "c" else (self.enc.flat if (which == "a" and self.agent.train_feature) else None)
+        if fl is not None and fl.split is not None:
+            M.call("gad_split_weights", fl.packed, fl._split_layers, len(fl._split_layers), fl.split, on=on)
+
+    def _build_bc_plan(self, M, H, Mpre, ev_g):
+        """The BC step's main list, one stream (the backward plan forks its weight-gradient lane itself): result block cleared,
+        ONE upload of the Adam scalars, policy forward -> outputs -> cloning loss (coefficient 1, no critic term) -> backward ->
+        ONE optimiser launch (policy: arena -> grad, Adam, policy_target, max |parameter|; encoder: Adam when it trains,
+        num_batches_tracked + 1) -> the encoder's split-bf16 mirror -> result block to the pinned ring slot.  The two small
+        items in front do not need the inputs: they run before the list waits for the prefetch lane's geometry."""
+        MAIN = 0
+        M.zero(self.scal, on=MAIN)
+        H["hyper"] = M.memcpy(self.hyper_all.data_ptr(), self._hyper_ring[0].data_ptr(), 4 * self.hyper_all.numel(), on=MAIN)
+        M.wait_event(ev_g, on=MAIN)
+        M.extend(self.plans["p_fwd"], on=MAIN)
+        self._plan_policy_outputs(M, MAIN)
+        self._plan_actor_tail(M, H, False, None, MAIN, coef=1.0)
+        H["download"] = M.memcpy(self._scal_ring[0].data_ptr(), self.scal.data_ptr(), 4 * self.scal.numel(), on=MAIN)
+        return dict(plan=M, pre=Mpre, items=H, last={})
+
     def _stage_inputs(self, batch, st, pre):
-        """the inputs of a step into set `st` + its prefetch list `pre` (geometry of both cloud sets): stream waits on events
-        owned by other steps / producers, the uploads (or the one gather / copy launch of a device-resident minibatch), then
-        the replayed prefetch-lane launches.  The set must be the bound one (self.dbuf / self.geo*)."""
+        """the inputs of a step into set `st` + its prefetch list `pre` (geometry of both cloud sets; BC: of the one): stream
+        waits on events owned by other steps / producers, the uploads (or the one gather / copy launch of a device-resident
+        minibatch), then the replayed prefetch-lane launches.  The set must be the bound one (self.dbuf / self.geo*)."""
         main = torch.cuda.current_stream()
-        spre, spre2 = engine.side_stream(which=20), engine.side_stream(which=21)
+        spre2 = engine.side_stream(which=21)
+        spre = engine.side_stream(which=20) if self.has_critic else spre2       # (BC: one lane, there is no next-state chain)
         ready = batch.get("ready_event") if batch is not None else None
         if ready is None and batch is not None and ("replay_gather" in batch or (
                 torch.is_tensor(batch["point_state_batch"]) and batch["point_state_batch"].is_cuda)):
@@ -744,7 +808,7 @@ class FusedRuntime(object):
                 s_.wait_event(st["ev_free"])
             if ready is not None:                   # (a producer's event says when its device tensors are complete)
                 s_.wait_event(ready)
-        whole = batch is not None and "replay_gather" in batch          # one gather launch fills every buffer
+        whole = (batch is not None and "replay_gather" in batch) or not self.has_critic      # one launch / one lane fills every buffer
         first = ("next_point_state_batch", "time_batch")
         with torch.cuda.stream(spre):
             self.upload(batch, None if whole else first)
@@ -762,7 +826,7 @@ class FusedRuntime(object):
         (sample, update, read the losses, every iteration: core/train_test_offline.py:117-126) keep the GPU busy across its
         host synchronisation: core.train_test_offline.train_off_policy samples one minibatch ahead and calls this.
         Device-resident minibatches only (DeviceReplay.sample_lazy, CUDA tensors); -> False when nothing was staged."""
-        if not (STEP_PLAN and OVERLAP_PASSES and self.fused_optim and self.has_critic) or engine.serial() or batch is None:
+        if not self._replays() or engine.serial() or batch is None:
             return False
         dev_batch = "replay_gather" in batch or (torch.is_tensor(batch.get("point_state_batch")) and batch["point_state_batch"].is_cuda)
         if not dev_batch or len(self._sets) < 2:
@@ -770,15 +834,18 @@ class FusedRuntime(object):
         # DEFERRED to the end of the next ddpg_step's enqueue: the prefetch lanes share a hardware queue with the value pass and the
         # critic's weight-gradient lane (engine._PHYS), so launches enqueued NOW would sit in front of that step's value pass
         # (measured: 365 -> 350 steps/s); enqueued behind the step they run beside its tail, which is where the run-ahead loop has them
+        if BC_PREFETCH_EARLY and not self.has_critic:
+            self._sets[self._set]["prefetched"] = None
+            return self._prefetch_now(batch, self._set)
         self._next_batch = batch
         return True
 
-    def _prefetch_now(self, batch):
-        if self._sets[(self._set + 1) % len(self._sets)].get("prefetched") is not None:
+    def _prefetch_now(self, batch, nxt=None):
+        nxt = (self._set + 1) % len(self._sets) if nxt is None else nxt
+        if self._sets[nxt].get("prefetched") is not None:
             return False
         bound = self._set
-        nxt = (self._set + 1) % len(self._sets)
-        ent = self._step_plan(nxt, True)                     # (the prefetch list is the same for both step kinds)
+        ent = self._step_plan(nxt, self.has_critic)          # (the prefetch list is the same for both step kinds; BC has one kind)
         st = self._bind_set(nxt)
         try:
             self._stage_inputs(batch, st, ent["pre"])
@@ -793,16 +860,10 @@ class FusedRuntime(object):
         ag = self.agent
         st = self._sets[self._set]
         ent = self._step_plan(self._set, policy_step)
-        M, H, last = ent["plan"], ent["items"], ent["last"]
         self._cur_batch = batch
         main = torch.cuda.current_stream()
         sc = engine.side_stream(which=3)
-        engine.apply_lane_priorities(main)
-        staged, st["prefetched"] = st.get("prefetched"), None
-        if staged is None or staged is not batch:
-            self._stage_inputs(batch, st, ent["pre"])
-        elif isinstance(batch, dict) and "uploaded_event" in batch:
-            batch["uploaded_event"] = st["ev_up"]
+        self._take_inputs(batch, st, ent)
         # the TD3 noise: torch's device generator (or the injected draw), ordered after the previous step's reader
         self._ev[0].record(main)
         sc.wait_event(self._ev[0])
@@ -826,14 +887,43 @@ class FusedRuntime(object):
         idx = sum(1 for m in ag.mix_milestones if ag.update_step > m)
         level = float(ag.action_noise * ag.noise_ratio_list[min(len(ag.noise_ratio_list) - 1, idx)])
         ratio = float(ag.mix_policy_ratio)
-        want = {("noise", 3): level, ("noise", 4): int(normal_noise), ("actor_loss", 8): 1.0 - ratio, ("ac_loss", 4): ratio,
-                ("hyper", 1): self._hyper_ring[self._slot].data_ptr(), ("download", 0): self.scal_host.data_ptr()}
+        self._patch_and_run(ent, {("noise", 3): level, ("noise", 4): int(normal_noise), ("actor_loss", 8): 1.0 - ratio,
+                                  ("ac_loss", 4): ratio})
+        self._cur_batch = None
+
+    def _take_inputs(self, batch, st, ent):
+        """the step's inputs: staged now, unless prefetch_inputs() staged this very batch object into the set already"""
+        engine.apply_lane_priorities(torch.cuda.current_stream())
+        staged, st["prefetched"] = st.get("prefetched"), None
+        if staged is None or staged is not batch:
+            self._stage_inputs(batch, st, ent["pre"])
+        elif isinstance(batch, dict) and "uploaded_event" in batch:
+            batch["uploaded_event"] = st["ev_up"]
+
+    def _patch_and_run(self, ent, want):
+        """write what changed since the list last ran into it -- `want` {(item, argument index): value} plus the pinned ring slot
+        of the Adam scalars and of the result block -- and replay it"""
+        H, last = ent["items"], ent["last"]
+        want[("hyper", 1)] = self._hyper_ring[self._slot].data_ptr()
+        want[("download", 0)] = self.scal_host.data_ptr()
         for (name, index), v in want.items():
             if name in H and last.get((name, index)) != v:
                 Plan.patch(H[name], index, v)
                 last[(name, index)] = v
-        M.run()
-        self._cur_batch = None
+        ent["plan"].run()
+
+    def _bc_replay(self, batch):
+        """enqueue one BC update through its replayed launch list (_build_bc_plan).  Eager host work that remains: the staging of
+        the inputs (unless prefetch_inputs did it) and this step's Adam scalars, read from the torch optimisers now."""
+        ag = self.agent
+        st = self._sets[self._set]
+        ent = self._step_plan(self._set, False)
+        self._take_inputs(batch, st, ent)
+        self._adam_host(self.pol.flat, ag.policy_optim)
+        if ag.train_feature:
+            self._adam_host(self.enc.flat, ag.state_feat_encoder_optim)
+        self._optim_select("a", False)
+        self._patch_and_run(ent, {})
 
     def _ddpg_enqueue(self, batch, noise_u, policy_step):
         """enqueue one update step on the current stream + the side streams (no host synchronisation inside); ends with the
@@ -1032,14 +1122,40 @@ class FusedRuntime(object):
             self.venc.bump_batches_tracked(3 if policy_step else 2)
         self._download(sync=False)
 
-    def bc_step(self, batch):
+    def bc_step(self, batch, sync=True):
+        """one BC update.  sync=False: return a PendingStep right after the enqueue (ddpg_step's contract: up to
+        engine.HOST_RING - 1 steps ahead).  The step is one replayed launch list (_bc_replay) unless _replays() says otherwise."""
+        slot = self._begin_step(alternate=True)
+        fused = self.fused_optim and self.dp is None     # (a data-parallel BC run keeps the separate optimiser launches)
+        replay = self._replays()
+        if replay:
+            self._bc_replay(batch)
+        else:
+            self._bc_enqueue(batch, fused)
+        return self._finish_step(slot, sync, replay, fused)
+
+    def _bc_enqueue(self, batch, fused):
+        """the BC step enqueued call by call on the current stream (no host synchronisation inside): what _bc_replay is
+        compared against; fused=False: the optimiser phase as separate Adam / target / statistics launches"""
         ag, d, P = self.agent, self.dbuf, self.plans
         B = self.B
-        self._begin_step()
+        st = self._sets[self._set]
+        main = torch.cuda.current_stream()
+        if st.get("prefetched") is not None:             # (staged for the replayed path, which was switched off since: dropped)
+            main.wait_stream(engine.side_stream(which=21))
+            st["prefetched"] = None
         self.upload(batch)
+        st["ev_up"].record(main)
+        if isinstance(batch, dict) and "uploaded_event" in batch:   # (PrefetchSampler: see _stage_inputs)
+            batch["uploaded_event"] = st["ev_up"]
         if self.dp is not None:
             self.dp.set_counts(batch)
         self.scal.zero_()
+        if fused:                                        # this step's Adam scalars of both networks: one upload
+            self._adam_host(self.pol.flat, ag.policy_optim)
+            if ag.train_feature:
+                self._adam_host(self.enc.flat, ag.state_feat_encoder_optim)
+            self.hyper_all.copy_(self._hyper_ring[self._slot], non_blocking=True)
         self.geo.run(d["point_state_batch"])
         P["p_fwd"].run()
         self._policy_outputs()
@@ -1048,13 +1164,16 @@ class FusedRuntime(object):
                  self.inv_n_actor(), self.hs_p.g_out, engine._ptr(self.scal, 4))
         P["p_bwd"].run()
         self._reduce([self.pol.flat, self.enc.flat], "a")      # (bucketed: the early bucket left from the plan's hook)
-        self._adam(self.pol.flat, ag.policy_optim)
-        if ag.train_feature:
-            self._adam(self.enc.flat, ag.state_feat_encoder_optim)
-        self._target_updates()
-        self._stats()
-        self.enc.bump_batches_tracked(1)
-        return self._download()
+        if fused:
+            self._optim_phase("a", False)                      # (carries the encoder's num_batches_tracked + 1)
+        else:
+            self._adam(self.pol.flat, ag.policy_optim)
+            if ag.train_feature:
+                self._adam(self.enc.flat, ag.state_feat_encoder_optim)
+            self._target_updates()
+            self._stats()
+            self.enc.bump_batches_tracked(1)
+        self._download(sync=False)
 
     def _policy_outputs(self):
         """pi = tanh(mean) * scale and the aux pose (unit quaternion + translation) when the head has one"""
