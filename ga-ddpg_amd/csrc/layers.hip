@@ -17,7 +17,8 @@ extern "C" int gad_bn_finalize(const double* stat_sum, const double* stat_sq, in
                                float* running_mean, float* running_var, float* scale, float* shift, float* mean,
                                float* istd, void* stream) {
     GAD_REQUIRE(stat_sum && stat_sq && gamma && beta && scale && shift, GAD_ERR_NULL, "bn_finalize: null pointer");
-    GAD_REQUIRE(C >= 1 && count >= 1.0, GAD_ERR_SHAPE, "bn_finalize: bad shape");
+    GAD_REQUIRE(C >= 0 && count >= 1.0, GAD_ERR_SHAPE, "bn_finalize: C=%d count=%g", C, count);
+    if (C == 0) return GAD_OK;
     gad_bn_fin b;
     b.stat_sum = stat_sum; b.stat_sq = stat_sq; b.stat_stride = stat_stride; b.count = count; b.gamma = gamma; b.beta = beta;
     b.eps = eps; b.momentum = momentum; b.running_mean = running_mean; b.running_var = running_var; b.scale = scale;
@@ -43,6 +44,8 @@ extern "C" int gad_bn_eval_affine(const float* gamma, const float* beta, const f
                                   const float* running_var, int C, float eps, float* scale, float* shift,
                                   void* stream) {
     GAD_REQUIRE(gamma && beta && running_mean && running_var && scale && shift, GAD_ERR_NULL, "bn_eval_affine: null pointer");
+    GAD_REQUIRE(C >= 0, GAD_ERR_SHAPE, "bn_eval_affine: C=%d", C);
+    if (C == 0) return GAD_OK;
     hipLaunchKernelGGL(bn_eval_affine_kernel, dim3(gad_cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, gamma, beta,
                        running_mean, running_var, C, eps, scale, shift);
     GAD_CHECK_LAUNCH("bn_eval_affine");
@@ -69,7 +72,8 @@ __global__ __launch_bounds__(256) void bn_running_update_kernel(const float* __r
 extern "C" int gad_bn_running_update(const float* mean, const float* istd, const float* count, int C, float eps,
                                      float momentum, float* running_mean, float* running_var, void* stream) {
     GAD_REQUIRE(mean && istd && count && running_mean && running_var, GAD_ERR_NULL, "bn_running_update: null pointer");
-    if (C <= 0) return GAD_OK;
+    GAD_REQUIRE(C >= 0, GAD_ERR_SHAPE, "bn_running_update: C=%d", C);
+    if (C == 0) return GAD_OK;
     hipLaunchKernelGGL(bn_running_update_kernel, dim3(gad_cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, mean, istd, count,
                        C, eps, momentum, running_mean, running_var);
     GAD_CHECK_LAUNCH("bn_running_update");
@@ -174,7 +178,8 @@ extern "C" int gad_segment_pool(const float* z, int z_pitch, int C, const float*
     GAD_REQUIRE(z && grp_off && out, GAD_ERR_NULL, "segment_pool: null pointer");
     GAD_REQUIRE((scale == nullptr) == (shift == nullptr), GAD_ERR_NULL, "segment_pool: scale and shift come together");
     GAD_REQUIRE(z_pitch % 4 == 0, GAD_ERR_SHAPE, "segment_pool: row pitch %d must be a multiple of 4", z_pitch);
-    if (G <= 0 || C <= 0) return GAD_OK;
+    GAD_REQUIRE(C >= 0 && z_pitch >= C, GAD_ERR_SHAPE, "segment_pool: C=%d, row pitch %d (rows would overlap)", C, z_pitch);
+    if (G <= 0 || C == 0) return GAD_OK;
     int gx = gad_cdiv(G, 4);
     if (gx > 2048) gx = 2048;
 #define LAUNCH_POOL(QPR, NQ)                                                                                      \
@@ -260,9 +265,10 @@ extern "C" int gad_pool_finalize(uint64_t* key, int C, int G, const int32_t* grp
                                  float* scale, float* shift, float* mean, float* istd, float* out, int32_t* argmax,
                                  float* zmax, void* stream) {
     GAD_REQUIRE(key && grp_off && gamma && scale && shift && out, GAD_ERR_NULL, "pool_finalize: null pointer");
-    GAD_REQUIRE(C >= 4 && C % 4 == 0, GAD_ERR_SHAPE, "pool_finalize: C=%d must be a positive multiple of 4", C);
-    GAD_REQUIRE(!stat_sum || (stat_sq && beta && count >= 1.0), GAD_ERR_NULL, "pool_finalize: statistics need stat_sq, beta, count");
-    if (G <= 0) return GAD_OK;
+    GAD_REQUIRE(C >= 0 && C % 4 == 0, GAD_ERR_SHAPE, "pool_finalize: C=%d must be a multiple of 4", C);
+    GAD_REQUIRE(!stat_sum || (stat_sq && beta), GAD_ERR_NULL, "pool_finalize: statistics need stat_sq and beta");
+    GAD_REQUIRE(!stat_sum || count >= 1.0, GAD_ERR_SHAPE, "pool_finalize: count=%g", count);
+    if (G <= 0 || C == 0) return GAD_OK;
     gad_bn_fin b;
     b.stat_sum = stat_sum; b.stat_sq = stat_sq; b.stat_stride = stat_stride; b.count = count; b.gamma = gamma; b.beta = beta;
     b.eps = eps; b.momentum = momentum; b.running_mean = running_mean; b.running_var = running_var; b.scale = scale;
@@ -292,6 +298,8 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
 extern "C" int gad_affine_act(const float* z, int z_pitch, int rows, int C, const float* scale, const float* shift,
                               int relu, float* out, int out_pitch, void* stream) {
     GAD_REQUIRE(z && out, GAD_ERR_NULL, "affine_act: null pointer");
+    GAD_REQUIRE(rows >= 0 && C >= 0 && z_pitch >= C && out_pitch >= C, GAD_ERR_SHAPE,
+                "affine_act: rows=%d C=%d, row pitches %d / %d (rows would overlap)", rows, C, z_pitch, out_pitch);
     const long long total = (long long)rows * C;
     if (total == 0) return GAD_OK;
     hipLaunchKernelGGL(affine_act_kernel, dim3(gad_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, z, z_pitch, C,
@@ -395,8 +403,8 @@ extern "C" int gad_pool_bwd_stats(float* dout, const int32_t* argmax, int G, int
                                   const float* zmax, void* stream) {
     GAD_REQUIRE(dout && (zmax || (argmax && z)) && scale && shift && mean && istd && dbeta && dgamma, GAD_ERR_NULL,
                 "pool_bwd_stats: null pointer");
-    GAD_REQUIRE(C % 32 == 0 && (C <= 256 ? 256 % C == 0 : C % 256 == 0), GAD_ERR_SHAPE, "pool_bwd_stats: C=%d", C);
-    if (G == 0) return GAD_OK;
+    GAD_REQUIRE(C >= 0 && C % 32 == 0 && (C == 0 || (C <= 256 ? 256 % C == 0 : C % 256 == 0)), GAD_ERR_SHAPE, "pool_bwd_stats: C=%d", C);
+    if (G <= 0 || C == 0) return GAD_OK;
     const int cpb = C < 256 ? C : 256, gl = 256 / cpb;
     int gy = gad_cdiv(G, gl * 4);
     if (gy > 512) gy = 512;                       // (1024 / 2048 workgroups: -0.5 / -1 % steps/s -- more same-address atomics)
@@ -431,6 +439,8 @@ extern "C" int gad_bn_bwd_coef(const double* dbeta, const double* dgamma, int st
                                const float* istd, int C, double count, float* coefP, float* coefQ, float* coefS,
                                double* gacc_gamma, double* gacc_beta, void* stream) {
     GAD_REQUIRE(dbeta && dgamma && scale && mean && istd && coefP && coefQ && coefS, GAD_ERR_NULL, "bn_bwd_coef: null pointer");
+    GAD_REQUIRE(C >= 0 && count >= 1.0, GAD_ERR_SHAPE, "bn_bwd_coef: C=%d count=%g", C, count);
+    if (C == 0) return GAD_OK;
     gad_bn_bwd b;
     b.dbeta = dbeta; b.dgamma = dgamma; b.stat_stride = stat_stride; b.count = count; b.mean = mean; b.istd = istd;
     b.gacc_gamma = gacc_gamma; b.gacc_beta = gacc_beta; b.accumulate = 1;

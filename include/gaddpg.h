@@ -51,7 +51,10 @@ int gad_abi_version(void);                 /* bumped on any signature change or 
                                             * action_bias in gad_policy_outputs;
                                             * 12: the Adam `hyper` block is GAD_ADAM_HYPER = 10 floats (1 - beta1, 1 - beta2
                                             * appended); added under 12 without a bump (no existing signature or struct
-                                            * layout changed): gad_replay_gather_multi, gad_replay_relabel_goals        */
+                                            * layout changed): gad_replay_gather_multi, gad_replay_relabel_goals; the
+                                            * argument checks of the BatchNorm / pool entry points below (a channel count of 0
+                                            * is GAD_OK without a launch, a negative one, a row pitch < C or a count < 1 is
+                                            * GAD_ERR_SHAPE): calls that were valid before behave as before             */
 /* diagnostics: which kernel family the last gad_gemm_fwd / _dx / _dw / _bwd call routed to ("gemm_fwd(stream)",
  * "gemm_dx(wide)", "gemm_bwd(stream)", "gemm_dw" = generic tile kernel, ...); bench.py labels its per-kernel table
  * with it instead of restating the routing rules.                                                  */
@@ -274,7 +277,8 @@ int gad_gemm_fwd(const gad_gemm_fwd_args* host_args, void* stream);
 
 /* train-mode BatchNorm finalisation: mean/var from the f64 sums over `count` rows (duplicates
  * included), scale = gamma*istd, shift = beta - mean*scale, running stats momentum update
- * (unbiased variance), saves mean/istd for the backward pass.                                   */
+ * (unbiased variance; count == 1: the biased one), saves mean/istd (nullable) for the backward pass.
+ * All the BatchNorm entry points: C == 0 returns GAD_OK without a launch, C < 0 or count < 1 is GAD_ERR_SHAPE.   */
 int gad_bn_finalize(const double* stat_sum, const double* stat_sq, int stat_stride, const float* gamma,
                     const float* beta, int C, double count, float eps, float momentum,
                     float* running_mean /*nullable*/, float* running_var /*nullable*/,
@@ -292,7 +296,8 @@ int gad_bn_eval_affine(const float* gamma, const float* beta, const float* runni
                        void* stream);
 
 /* segment max-pool over each group's rows of act(scale*z+shift): out (G,C) point-major,
- * argmax (G,C) = global row index of the first maximum.                                          */
+ * argmax (G,C) = global row index of the first maximum (nullable); a group without rows gives 0 and grp_off[g].  C is one of 8, 16, 32, 64, 128, 256, 512, 1024;
+ * z_pitch is a multiple of 4 and >= C (anything else: GAD_ERR_SHAPE); scale and shift are both given or both NULL.   */
 int gad_segment_pool(const float* z, int z_pitch, int C, const float* scale, const float* shift,
                      const int32_t* grp_off, int G, float* out, int32_t* argmax, void* stream);
 
@@ -308,7 +313,8 @@ int gad_pool_finalize(uint64_t* key, int C, int G, const int32_t* grp_off, const
                       float* mean /*nullable*/, float* istd /*nullable*/, float* out, int32_t* argmax, float* zmax,
                       void* stream);
 
-/* apply act(scale*z+shift) elementwise -> out (rows,C) (used at API boundaries only)            */
+/* apply act(scale*z+shift) elementwise -> out (rows,C) (used at API boundaries only); z_pitch, out_pitch >= C
+ * (GAD_ERR_SHAPE otherwise: rows would overlap); scale == NULL: no affine map                      */
 int gad_affine_act(const float* z, int z_pitch, int rows, int C, const float* scale,
                    const float* shift, int relu, float* out, int out_pitch, void* stream);
 
@@ -359,14 +365,20 @@ typedef struct {
 /* mask_in_place != 0: dout[g][c] is also overwritten with its ReLU-masked value (0 where the arg-max row's
  * activation is not positive), so that the layer's dX / dW can take it as `premasked`.             */
 /* zmax (nullable): (G,C) raw value of every arg-max row as saved by gad_pool_finalize -- read instead of gathering
- * z[argmax] (argmax / z may then be NULL).                                                          */
+ * z[argmax] (argmax / z may then be NULL).
+ * Channels with scale == 0 (gamma == 0): every row of a group ties, so the routed row is the group's FIRST row while zmax
+ * holds the value of the key's row.  With argmax and z given next to zmax, x_hat of such a channel is gathered from the
+ * routed row, as the reference does.  With zmax alone there is no row to gather: x_hat comes from zmax, so dgamma of a
+ * gamma == 0 channel is summed over the key's rows instead of the first rows (dbeta and the mask do not depend on it) --
+ * a caller that trains gamma through zero passes argmax and z as well.
+ * C: a multiple of 32 that divides 256 or is a multiple of 256.                                      */
 int gad_pool_bwd_stats(float* dout, const int32_t* argmax, int G, int C, const float* z,
                        int z_pitch, const float* scale, const float* shift, const float* mean,
                        const float* istd, double* dbeta, double* dgamma, int stat_stride,
                        int mask_in_place, const float* zmax, void* stream);
 
 /* BN backward coefficients from (dbeta,dgamma): P,Q,S above; also accumulates dgamma/dbeta into
- * the f64 gradient arena slots gacc_gamma/gacc_beta (nullable).                                 */
+ * the f64 gradient arena slots gacc_gamma/gacc_beta (nullable).  count >= 1 (GAD_ERR_SHAPE otherwise).   */
 int gad_bn_bwd_coef(const double* dbeta, const double* dgamma, int stat_stride, const float* scale,
                     const float* mean, const float* istd, int C, double count, float* coefP,
                     float* coefQ, float* coefS, double* gacc_gamma, double* gacc_beta,
