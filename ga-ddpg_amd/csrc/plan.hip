@@ -86,6 +86,9 @@ const std::vector<reg_entry>& registry() {
         GAD_PLAN_ENTRY(gad_ball_query)
         GAD_PLAN_ENTRY(gad_group_points)
         GAD_PLAN_ENTRY(gad_group_points_grad)
+        GAD_PLAN_ENTRY(gad_three_nn)
+        GAD_PLAN_ENTRY(gad_three_interpolate)
+        GAD_PLAN_ENTRY(gad_three_interpolate_grad)
         GAD_PLAN_ENTRY(gad_query_and_group)
         GAD_PLAN_ENTRY(gad_prep_points)
         GAD_PLAN_ENTRY(gad_rows_from_ball_query)

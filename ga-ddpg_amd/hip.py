@@ -132,6 +132,9 @@ def lib():
         L.gad_abi_version.restype = C.c_int
         L.gad_last_kernel.restype = C.c_char_p
         L.gad_plan_entry_name.restype = C.c_char_p
+        for name, argtypes in _SIGNATURES.items():
+            f = getattr(L, name)
+            f.argtypes, f.restype = argtypes, C.c_int
         _lib = L
         for name, v in OPTION_DEFAULTS.items():   # what THIS package runs with where the library's own default differs (explicit opt-in)
             check(L.gad_set_option(name.encode(), int(v)), "gad_set_option(%s)" % name)
@@ -146,6 +149,7 @@ def lib():
 EXPORTS = (
     "gad_abi_version", "gad_last_kernel", "gad_last_error", "gad_set_option", "gad_timing_slot", "gad_stream_priority", "gad_wall_clock_khz", "gad_grid_rows_hint", "gad_bn_running_update", "gad_replay_gather", "gad_replay_gather_multi", "gad_replay_relabel_goals", "gad_zero_buffers", "gad_furthest_point_sampling", "gad_gather_points",
     "gad_gather_points_grad", "gad_ball_query", "gad_group_points", "gad_group_points_grad",
+    "gad_three_nn", "gad_three_interpolate", "gad_three_interpolate_grad",
     "gad_query_and_group", "gad_prep_points", "gad_rows_from_ball_query", "gad_rows_group_all",
     "gad_gemm_fwd", "gad_bn_finalize", "gad_bn_eval_affine", "gad_segment_pool", "gad_pool_finalize", "gad_affine_act", "gad_transpose_batched",
     "gad_pool_bwd_stats", "gad_bn_bwd_coef", "gad_gemm_dx", "gad_gemm_dw", "gad_gemm_bwd", "gad_gemm_dw_reduce", "gad_critic_loss",
@@ -155,6 +159,15 @@ EXPORTS = (
     "gad_plan_create", "gad_plan_destroy", "gad_plan_size", "gad_plan_add_call", "gad_plan_add_wait", "gad_plan_add_record",
     "gad_plan_add_wait_event", "gad_plan_add_memset", "gad_plan_add_memcpy", "gad_plan_patch", "gad_plan_arm_timing", "gad_plan_run",
     "gad_plan_entry_count", "gad_plan_entry_name")
+
+
+# argument types of the feature-propagation entry points (include/gaddpg.h section A), set when the library loads: ctypes then
+# refuses a call whose argument count or kinds do not match
+_SIGNATURES = {
+    "gad_three_nn": [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp],
+    "gad_three_interpolate": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
+    "gad_three_interpolate_grad": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
+}
 
 
 class Ptr(int):

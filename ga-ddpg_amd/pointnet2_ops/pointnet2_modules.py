@@ -1,4 +1,4 @@
-"""pointnet2_ops.pointnet2_modules surface: PointnetSAModule / PointnetSAModuleMSG with upstream's
+"""pointnet2_ops.pointnet2_modules surface: PointnetSAModule / PointnetSAModuleMSG / PointnetFPModule with upstream's
 module tree (`groupers`, `mlps`; shared MLP = Sequential of [Conv2d 1x1 no-bias, BatchNorm2d, ReLU]
 triples) so reference checkpoints' keys `mlps.0.{0,1,3,4,6,7}.*` load unchanged.
 
@@ -6,7 +6,10 @@ forward(xyz (B,N,3), features (B,C,N)) -> (new_xyz (B,npoint,3) | None, (B,C',np
 set-abstraction path of libgaddpg (FPS, ball query, de-duplicated rows, FP32-MFMA shared MLP with
 train-mode BatchNorm statistics, segment max-pool); see ga_ddpg_amd.sa_function for the autograd
 wrapper.  Modules hold ordinary nn.Parameters; the fused update step (core.agent) re-homes them into
-flat buffers."""
+flat buffers.
+
+PointnetFPModule (feature propagation, `mlp` = one shared MLP, keys `mlp.{0,1,3,4,...}.*`): three_nn and three_interpolate of
+libgaddpg, the shared MLP as torch modules."""
 import torch.nn as nn
 
 from . import pointnet2_utils
@@ -96,3 +99,28 @@ class PointnetSAModuleMSG(nn.Module):
 class PointnetSAModule(PointnetSAModuleMSG):
     def __init__(self, mlp, npoint=None, radius=None, nsample=None, bn=True, use_xyz=True):
         super().__init__(npoint=npoint, radii=[radius], nsamples=[nsample], mlps=[mlp], bn=bn, use_xyz=use_xyz)
+
+
+class PointnetFPModule(nn.Module):
+    """feature propagation: the features of `known` (B,m,3) are carried to `unknown` (B,n,3) by inverse-distance weights over the
+    three nearest known points (pointnet2_utils.three_nn / three_interpolate: libgaddpg section A kernels, differentiable in the
+    features), concatenated with the skip features and passed through the shared MLP as torch modules -- the route
+    _generic_forward takes for the non-fused set-abstraction forms"""
+
+    def __init__(self, mlp, bn=True):
+        super().__init__()
+        self.mlp = build_shared_mlp(list(mlp), bn)
+
+    def forward(self, unknown, known, unknow_feats, known_feats):
+        """unknown (B,n,3), known (B,m,3) | None, unknow_feats (B,C1,n) | None, known_feats (B,C2,m) -> (B,mlp[-1],n)"""
+        import torch
+        if known is not None:
+            dist, idx = pointnet2_utils.three_nn(unknown, known)
+            w = 1.0 / (dist + 1e-8)
+            w = w / w.sum(dim=2, keepdim=True)
+            x = pointnet2_utils.three_interpolate(known_feats, idx, w)
+        else:
+            x = known_feats.expand(*known_feats.shape[:2], unknown.shape[1])
+        if unknow_feats is not None:
+            x = torch.cat([x, unknow_feats], dim=1)
+        return self.mlp(x.unsqueeze(-1)).squeeze(-1)

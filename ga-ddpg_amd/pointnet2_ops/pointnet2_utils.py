@@ -2,7 +2,7 @@
 
 Each function mirrors upstream's autograd.Function of the same name: same argument order, shapes,
 dtypes (indices are int32), contiguity / device checks raising RuntimeError, gradients only where
-upstream defines them (features of grouping_operation / gather_operation)."""
+upstream defines them (features of grouping_operation / gather_operation / three_interpolate)."""
 import torch
 import torch.nn as nn
 
@@ -84,6 +84,53 @@ class _Group(torch.autograd.Function):
 
 def grouping_operation(features, idx):
     return _Group.apply(features, idx)
+
+
+def three_nn(unknown, known):
+    """unknown (B,n,3), known (B,m,3) float32 CUDA contiguous -> (dist (B,n,3) float32, idx (B,n,3) int32): the three nearest
+    known points of every query point, nearest first, ties to the lower index; dist is the Euclidean distance (the square root of
+    what gad_three_nn returns).  Neither output is differentiable."""
+    _check(unknown, known)
+    if unknown.dtype != torch.float32 or known.dtype != torch.float32:
+        raise RuntimeError("unknown and known must be float tensors")
+    B, n, _ = unknown.shape
+    m = known.shape[1]
+    dist2 = torch.empty(B, n, 3, dtype=torch.float32, device=unknown.device)
+    idx = torch.empty(B, n, 3, dtype=torch.int32, device=unknown.device)
+    hip.call("gad_three_nn", unknown.detach(), known.detach(), B, n, m, dist2, idx)
+    return torch.sqrt(dist2), idx
+
+
+class _ThreeInterpolate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, idx, weight):
+        _check(features, idx, weight)
+        if features.dtype != torch.float32 or weight.dtype != torch.float32:
+            raise RuntimeError("features and weight must be float tensors")
+        if idx.dtype != torch.int32:
+            raise RuntimeError("idx must be an int tensor")
+        B, C, m = features.shape
+        n = idx.shape[1]
+        out = torch.empty(B, C, n, dtype=torch.float32, device=features.device)
+        hip.call("gad_three_interpolate", features, idx, weight, B, C, m, n, out)
+        ctx.save_for_backward(idx, weight)
+        ctx.m = m
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        idx, weight = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        B, C, n = grad_out.shape
+        g = torch.empty(B, C, ctx.m, dtype=torch.float32, device=grad_out.device)
+        hip.call("gad_three_interpolate_grad", grad_out, idx, weight, B, C, n, ctx.m, g)
+        return g, None, None
+
+
+def three_interpolate(features, idx, weight):
+    """features (B,C,m), idx (B,n,3) int32, weight (B,n,3) -> (B,C,n): the weighted sum of three feature columns per point.
+    The gradient flows to `features` only."""
+    return _ThreeInterpolate.apply(features, idx, weight)
 
 
 def query_and_group(radius, nsample, xyz, new_xyz, features):

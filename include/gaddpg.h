@@ -14,7 +14,7 @@
  *
  * Section A replaces the C++/CUDA extension `pointnet2_ops._ext` that reference core/networks.py:10
  * and core/utils.py:32 reach through pointnet2_ops.pointnet2_utils (upstream bindings.cpp:
- * furthest_point_sampling, gather_points[_grad], ball_query, group_points[_grad]).
+ * furthest_point_sampling, gather_points[_grad], ball_query, group_points[_grad], three_nn, three_interpolate[_grad]).
  * Sections B-E are the fused update-step path that sits behind core/networks.py:65-92,182-371,
  * core/ddpg.py:119-185, core/agent.py:127-139,192-259, core/loss.py:17-31 and core/utils.py:750-774.
  */
@@ -54,7 +54,9 @@ int gad_abi_version(void);                 /* bumped on any signature change or 
                                             * layout changed): gad_replay_gather_multi, gad_replay_relabel_goals; the
                                             * argument checks of the BatchNorm / pool entry points below (a channel count of 0
                                             * is GAD_OK without a launch, a negative one, a row pitch < C or a count < 1 is
-                                            * GAD_ERR_SHAPE): calls that were valid before behave as before             */
+                                            * GAD_ERR_SHAPE): calls that were valid before behave as before; gad_three_nn,
+                                            * gad_three_interpolate, gad_three_interpolate_grad (additive: section A now
+                                            * covers all nine operators of pointnet2_ops._ext)                          */
 /* diagnostics: which kernel family the last gad_gemm_fwd / _dx / _dw / _bwd call routed to ("gemm_fwd(stream)",
  * "gemm_dx(wide)", "gemm_bwd(stream)", "gemm_dw" = generic tile kernel, ...); bench.py labels its per-kernel table
  * with it instead of restating the routing rules.                                                  */
@@ -148,6 +150,31 @@ int gad_group_points(const float* points, const int32_t* idx, int B, int C, int 
                      float* out, void* stream);
 int gad_group_points_grad(const float* grad_out, const int32_t* idx, int B, int C, int N, int M,
                           int S, float* grad_points, void* stream);
+
+/* three_nn(unknown (B,n,3), known (B,m,3)) -> dist2 (B,n,3) f32, idx (B,n,3) i32: for every query point the three known points
+ * of its sample that are smallest under the order (d, index), listed in ascending order, with
+ *   d = ((ux-x)*(ux-x) + (uy-y)*(uy-y)) + (uz-z)*(uz-z)
+ * in float32, every operation individually rounded (no FMA contraction): what upstream's three_nn_kernel computes with its
+ * sequential strict-< insertion -- ties go to the lower index; a d that is NaN (or +inf) is never selected.  With m < 3 the
+ * unfilled slots hold idx = 0 and dist2 = +inf (upstream's 1e40 double stored as a float).  The outputs are SQUARED distances:
+ * the square root is taken by the caller (pointnet2_utils.three_nn), as upstream does.  No limit on n or m beyond int32.
+ * B * n == 0: GAD_OK without a launch; otherwise m < 1 is GAD_ERR_SHAPE, as is any negative size.                            */
+int gad_three_nn(const float* unknown, const float* known, int B, int n, int m, float* dist2, int32_t* idx, void* stream);
+
+/* three_interpolate(points (B,C,m), idx (B,n,3), weight (B,n,3)) -> out (B,C,n):
+ *   out[b,c,i] = (w0 * f[idx0] + w1 * f[idx1]) + w2 * f[idx2],   f = points[b,c,:]
+ * float32, every operation individually rounded, in that order.  Indices are NOT range-checked (as in gad_group_points): the
+ * caller passes 0 <= idx < m.  C == 0 or n == 0: GAD_OK without a launch.
+ * _grad: grad_points[b,c,idx[b,i,k]] += grad_out[b,c,i] * weight[b,i,k] over all (i, k).  The call writes EVERY element of
+ * grad_points (B,C,m) -- the caller does not clear it.  The adds are f32 atomics in no fixed order (upstream torch::zeros +
+ * atomicAdd): in LDS, one workgroup per chunk of rows, for m <= 8192; behind a clearing pass on the stream, in global memory,
+ * beyond.  Option "deterministic": every destination is written by one thread that applies its entries in ascending
+ * i * 3 + k order, each product rounded before it is added -- bit-equal to a sequential float32 accumulation from 0 in that order,
+ * whatever the scheduling, for any m.  Both: m < 1 with B * C * n > 0 is GAD_ERR_SHAPE, as is any negative size.            */
+int gad_three_interpolate(const float* points, const int32_t* idx, const float* weight, int B, int C, int m, int n,
+                          float* out, void* stream);
+int gad_three_interpolate_grad(const float* grad_out, const int32_t* idx, const float* weight, int B, int C, int n, int m,
+                               float* grad_points, void* stream);
 
 /* QueryAndGroup in one pass (ball_query + group xyz + recentre + group features + concat):
  * out (B,3+C,M,S) exactly as pointnet2_utils.QueryAndGroup(use_xyz=True) returns it; idx as above.
