@@ -220,3 +220,23 @@ def pack_pose_rot_first(pose):
     packed[:4] = safemat2quat(pose[:3, :3])
     return packed
 
+
+def regularize_pc_point_count(pc, npoints, use_farthest_point=False):
+    """Bring the (n, C) cloud `pc` to exactly `npoints` rows.  A larger cloud is cut down, by furthest point sampling over its
+    first three columns on the GPU when `use_farthest_point` (the result is then a float32 array), else by a draw without
+    replacement; a smaller one is padded with rows drawn with replacement; one of the right size is returned as it is.  The
+    np.random calls are the reference's, so a seeded script draws the same rows."""
+    n = pc.shape[0]
+    if n > npoints:
+        if use_farthest_point:
+            from ..pointnet2_ops.pointnet2_utils import furthest_point_sample, gather_operation
+            cloud = torch.from_numpy(pc).cuda()[None].float()
+            idx = furthest_point_sample(cloud[..., :3].contiguous(), npoints)
+            picked = gather_operation(cloud.transpose(1, 2).contiguous(), idx)
+            return picked[0].T.detach().cpu().numpy()
+        keep = np.random.choice(range(n), size=npoints, replace=False)
+        return pc[keep, :]
+    if n < npoints:
+        extra = np.random.choice(range(n), size=npoints - n)
+        return np.concatenate((pc, pc[extra, :]), axis=0)
+    return pc

@@ -371,7 +371,8 @@ extern "C" int gad_furthest_point_sampling(const float* xyz, int B, int N, int M
                                            float* new_xyz, void* stream) {
     GAD_REQUIRE(xyz && idx, GAD_ERR_NULL, "fps: null pointer");
     GAD_REQUIRE(B >= 0 && N >= 1 && M >= 0 && N <= 16384 && N <= 65535, GAD_ERR_SHAPE, "fps: unsupported shape B=%d N=%d M=%d", B, N, M);
-    // (upstream samples without replacement from N points: npoint > N repeats index 0 there; the pick buffer below is sized by M)
+    // (upstream accepts npoint > N: once every distance is 0 its tie rule picks the index.  This kernel keeps the M picks next to
+    // the cloud in LDS and refuses the shape; gad_fps_tiled below takes it)
     GAD_REQUIRE(M <= N, GAD_ERR_SHAPE, "fps: M=%d picks from N=%d points", M, N);
     if (B == 0 || M == 0) return GAD_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -407,6 +408,135 @@ extern "C" int gad_furthest_point_sampling(const float* xyz, int B, int N, int M
     }
 #undef FPS_LAUNCH
     GAD_CHECK_LAUNCH("fps");
+    return GAD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// furthest point sampling of clouds that do not fit one workgroup (raw depth clouds: 1e5 .. 3e5 points; npoint > N)
+// ------------------------------------------------------------------------------------------------
+// A cloud is cut into `groups` contiguous slices, one workgroup each; the running minimum distances (upstream's `temp` tensor)
+// live in the caller's workspace, -1 marking a point the skip rule excludes (min(d, -1) stays -1, and -1 is never a candidate).
+// ONE LAUNCH PER ROUND: round j reads the pick of round j - 1 from that round's slot, updates its slice, reduces it to one packed
+// (distance bits, inverted key) maximum and folds it into slot j with a 64-bit device-scope atomic max.  The stream orders the
+// rounds; no workgroup ever waits for another inside a launch (no grid barrier, no spinning: a grid-wide sync measured 2-3x a
+// dependent launch on this part, profiles/HISTORY_design_notes_r01_r04.md).  A slot is written by round j only and read by the
+// launches after it, so the maximum of unsigned integers is the same whatever the arrival order: the picks are deterministic.
+// The key is (bit-reversed (k mod tie_bs) << 22) | k -- 9 + 22 bits, hence the cap on N; slot value 0 = "no candidate" = index 0.
+#define FPS_TILED_MAX_N (1 << 22)
+#define FPS_TILED_T 256
+#define FPS_TILED_SLICE 1024                       // points per workgroup when the caller passes groups = 0 (profiles/fps_tiled.txt)
+
+__device__ __forceinline__ int fps_tiled_pick(unsigned long long best) {
+    return best ? (int)(~(unsigned)best & (unsigned)(FPS_TILED_MAX_N - 1)) : 0;
+}
+
+__global__ __launch_bounds__(FPS_TILED_T) void fps_tiled_init_kernel(const float* __restrict__ xyz, long long n_points,
+                                                                     float* __restrict__ temp, unsigned long long* __restrict__ slots,
+                                                                     long long n_slots) {
+    const long long stride = (long long)gridDim.x * FPS_TILED_T;
+    for (long long i = (long long)blockIdx.x * FPS_TILED_T + threadIdx.x; i < n_points; i += stride) {
+        const float* q = xyz + i * 3;
+        temp[i] = gad_sqnorm(q[0], q[1], q[2]) < 1e-3f ? -1.f : 1e10f;           // (the float form of upstream's compare: see fps_kernel)
+    }
+    for (long long i = (long long)blockIdx.x * FPS_TILED_T + threadIdx.x; i < n_slots; i += stride) slots[i] = 0ull;
+}
+
+__global__ __launch_bounds__(FPS_TILED_T) void fps_tiled_round_kernel(const float* __restrict__ xyz, int N, int M, int j, int groups,
+                                                                      int slice, int tie_bits, float* __restrict__ temp,
+                                                                      unsigned long long* __restrict__ slots) {
+    __shared__ unsigned long long red[FPS_TILED_T / 64];
+    const int b = blockIdx.x / groups, g = blockIdx.x - b * groups, tid = threadIdx.x;
+    const int k0 = g * slice, k1 = min(N, k0 + slice);
+    if (k0 >= k1) return;                                            // (workgroup-uniform: trailing slices of an uneven cut are empty)
+    const float* p = xyz + (size_t)b * N * 3;
+    float* t = temp + (size_t)b * N;
+    unsigned long long* s = slots + (size_t)b * M;
+    const int old = fps_tiled_pick(s[j - 1]);                        // (slot 0 stays 0: the first pick is index 0)
+    const float x1 = p[old * 3 + 0], y1 = p[old * 3 + 1], z1 = p[old * 3 + 2];
+    const unsigned tie_mask = (1u << tie_bits) - 1u;
+    unsigned long long best = 0ull;
+#pragma unroll 4
+    for (int k = k0 + tid; k < k1; k += FPS_TILED_T) {
+        float tv = t[k];
+        if (tv >= 0.f) {
+            const float d = gad_sqdist(p[k * 3 + 0], p[k * 3 + 1], p[k * 3 + 2], x1, y1, z1);
+            if (d < tv) {
+                tv = d;
+                t[k] = d;
+            }
+            const unsigned rev = tie_bits ? (__brev((unsigned)k & tie_mask) >> (32 - tie_bits)) : 0u;
+            const unsigned long long c = fps_pack(tv, (rev << 22) | (unsigned)k);
+            best = c > best ? c : best;
+        }
+    }
+    best = fps_wave_max(best);
+    if ((tid & 63) == 0) red[tid >> 6] = best;
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < FPS_TILED_T / 64; ++w) best = red[w] > best ? red[w] : best;
+        if (best) __hip_atomic_fetch_max(s + j, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+__global__ __launch_bounds__(FPS_TILED_T) void fps_tiled_write_kernel(const float* __restrict__ xyz, int N, int M, long long n_slots,
+                                                                      const unsigned long long* __restrict__ slots,
+                                                                      int32_t* __restrict__ idx, float* __restrict__ new_xyz) {
+    const long long stride = (long long)gridDim.x * FPS_TILED_T;
+    for (long long i = (long long)blockIdx.x * FPS_TILED_T + threadIdx.x; i < n_slots; i += stride) {
+        const int pick = fps_tiled_pick(slots[i]);
+        idx[i] = pick;
+        if (new_xyz) {
+            const float* q = xyz + ((i / M) * N + pick) * 3;
+            float* o = new_xyz + i * 3;
+            o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
+        }
+    }
+}
+
+// argument checks shared by the two entry points; *groups receives the workgroups per cloud in force
+static int fps_tiled_check(const char* who, int B, int N, int M, int* groups) {
+    GAD_REQUIRE(B >= 0 && N >= 1 && M >= 0, GAD_ERR_SHAPE, "%s: unsupported shape B=%d N=%d M=%d", who, B, N, M);
+    GAD_REQUIRE(N <= FPS_TILED_MAX_N, GAD_ERR_SHAPE, "%s: N=%d is over the cap of %d points (22 index bits of the arg-max key)", who, N,
+                FPS_TILED_MAX_N);
+    GAD_REQUIRE(*groups >= 0 && *groups <= N, GAD_ERR_SHAPE, "%s: groups=%d outside [0, N=%d]", who, *groups, N);
+    if (*groups == 0) *groups = gad_cdiv(N, FPS_TILED_SLICE);
+    // (hipLaunchKernelGGL takes the grid in threads: workgroups x 256 has to stay below 2^32)
+    GAD_REQUIRE((long long)B * *groups < (1ll << 23), GAD_ERR_SHAPE, "%s: a grid of B * groups = %d * %d workgroups overflows", who, B,
+                *groups);
+    return GAD_OK;
+}
+
+static long long fps_tiled_temp_bytes(int B, int N) { return ((long long)B * N * 4 + 255) & ~255ll; }
+
+extern "C" long long gad_fps_tiled_workspace_bytes(int B, int N, int M, int groups) {
+    const int rc = fps_tiled_check("fps_tiled_workspace_bytes", B, N, M, &groups);
+    if (rc != GAD_OK) return rc;
+    return fps_tiled_temp_bytes(B, N) + (long long)B * M * 8;       // temp (B,N) f32, then one 64-bit slot per cloud and round
+}
+
+extern "C" int gad_fps_tiled(const float* xyz, int B, int N, int M, int groups, int32_t* idx, float* new_xyz, void* workspace,
+                             void* stream) {
+    GAD_REQUIRE(xyz && idx, GAD_ERR_NULL, "fps_tiled: null pointer (xyz / idx)");
+    const int rc = fps_tiled_check("fps_tiled", B, N, M, &groups);
+    if (rc != GAD_OK) return rc;
+    if (B == 0 || M == 0) return GAD_OK;
+    GAD_REQUIRE(workspace, GAD_ERR_NULL, "fps_tiled: null pointer (workspace)");
+    GAD_REQUIRE((reinterpret_cast<size_t>(workspace) & 7) == 0, GAD_ERR_SHAPE, "fps_tiled: the workspace must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    float* temp = static_cast<float*>(workspace);
+    unsigned long long* slots = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + fps_tiled_temp_bytes(B, N));
+    const long long n_points = (long long)B * N, n_slots = (long long)B * M;
+    const int slice = gad_cdiv(N, groups), tie = fps_tie_bits(N);
+    const long long n_max = n_points > n_slots ? n_points : n_slots;
+    const int init_grid = (int)(gad_cdiv(n_max, FPS_TILED_T) < 4096 ? gad_cdiv(n_max, FPS_TILED_T) : 4096);
+    hipLaunchKernelGGL(fps_tiled_init_kernel, dim3(init_grid), dim3(FPS_TILED_T), 0, st, xyz, n_points, temp, slots, n_slots);
+    for (int j = 1; j < M; ++j)
+        hipLaunchKernelGGL(fps_tiled_round_kernel, dim3(B * groups), dim3(FPS_TILED_T), 0, st, xyz, N, M, j, groups, slice, tie, temp,
+                           slots);
+    const int out_grid = (int)(gad_cdiv(n_slots, FPS_TILED_T) < 4096 ? gad_cdiv(n_slots, FPS_TILED_T) : 4096);
+    hipLaunchKernelGGL(fps_tiled_write_kernel, dim3(out_grid), dim3(FPS_TILED_T), 0, st, xyz, N, M, n_slots, slots, idx, new_xyz);
+    GAD_CHECK_LAUNCH("fps_tiled");
     return GAD_OK;
 }
 

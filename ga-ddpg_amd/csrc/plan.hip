@@ -81,6 +81,7 @@ const std::vector<reg_entry>& registry() {
         std::vector<reg_entry> v;
         GAD_PLAN_ENTRY(gad_grid_rows_hint)
         GAD_PLAN_ENTRY(gad_furthest_point_sampling)
+        GAD_PLAN_ENTRY(gad_fps_tiled)
         GAD_PLAN_ENTRY(gad_gather_points)
         GAD_PLAN_ENTRY(gad_gather_points_grad)
         GAD_PLAN_ENTRY(gad_ball_query)

@@ -134,7 +134,7 @@ def lib():
         L.gad_plan_entry_name.restype = C.c_char_p
         for name, argtypes in _SIGNATURES.items():
             f = getattr(L, name)
-            f.argtypes, f.restype = argtypes, C.c_int
+            f.argtypes, f.restype = argtypes, _RESTYPES.get(name, C.c_int)
         _lib = L
         for name, v in OPTION_DEFAULTS.items():   # what THIS package runs with where the library's own default differs (explicit opt-in)
             check(L.gad_set_option(name.encode(), int(v)), "gad_set_option(%s)" % name)
@@ -148,6 +148,7 @@ def lib():
 
 EXPORTS = (
     "gad_abi_version", "gad_last_kernel", "gad_last_error", "gad_set_option", "gad_timing_slot", "gad_stream_priority", "gad_wall_clock_khz", "gad_grid_rows_hint", "gad_bn_running_update", "gad_replay_gather", "gad_replay_gather_multi", "gad_replay_relabel_goals", "gad_zero_buffers", "gad_furthest_point_sampling", "gad_gather_points",
+    "gad_fps_tiled_workspace_bytes", "gad_fps_tiled",
     "gad_gather_points_grad", "gad_ball_query", "gad_group_points", "gad_group_points_grad",
     "gad_three_nn", "gad_three_interpolate", "gad_three_interpolate_grad",
     "gad_query_and_group", "gad_prep_points", "gad_rows_from_ball_query", "gad_rows_group_all",
@@ -161,13 +162,18 @@ EXPORTS = (
     "gad_plan_entry_count", "gad_plan_entry_name")
 
 
-# argument types of the feature-propagation entry points (include/gaddpg.h section A), set when the library loads: ctypes then
-# refuses a call whose argument count or kinds do not match
+# argument types of the feature-propagation and tiled-sampling entry points (include/gaddpg.h section A), set when the library
+# loads: ctypes then refuses a call whose argument count or kinds do not match
 _SIGNATURES = {
+    "gad_fps_tiled_workspace_bytes": [C.c_int, C.c_int, C.c_int, C.c_int],
+    "gad_fps_tiled": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
     "gad_three_nn": [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp],
     "gad_three_interpolate": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
     "gad_three_interpolate_grad": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
 }
+
+
+_RESTYPES = {"gad_fps_tiled_workspace_bytes": C.c_longlong}       # every other entry point returns an int status
 
 
 class Ptr(int):

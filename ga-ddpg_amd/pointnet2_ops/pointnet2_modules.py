@@ -44,7 +44,12 @@ class PointnetSAModuleMSG(nn.Module):
     (_PointnetSAModuleBase.forward) over this package's operators: furthest_point_sample -> gather_operation -> QueryAndGroup /
     GroupAll (libgaddpg section A kernels, differentiable through their _grad counterparts) -> the shared MLP as torch modules ->
     max-pool over the neighbourhood.  Same results as upstream's module; the padded (B, C, npoint, nsample) tensor is materialised,
-    as it is there (no shipped GA-DDPG configuration builds these forms)."""
+    as it is there (no shipped GA-DDPG configuration builds these forms).
+
+    npoint and cloud size: the generic composition samples through pointnet2_utils.furthest_point_sample and takes what upstream
+    takes, npoint > N and clouds beyond one workgroup's LDS included.  The fused path calls gad_furthest_point_sampling directly
+    and keeps its refusals (include/gaddpg.h): N <= 16384, npoint <= N, (3N + npoint + 64) * 4 bytes within 160 KiB -- it raises
+    RuntimeError otherwise."""
 
     def __init__(self, npoint, radii, nsamples, mlps, bn=True, use_xyz=True):
         super().__init__()

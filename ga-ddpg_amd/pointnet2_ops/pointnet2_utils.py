@@ -2,7 +2,12 @@
 
 Each function mirrors upstream's autograd.Function of the same name: same argument order, shapes,
 dtypes (indices are int32), contiguity / device checks raising RuntimeError, gradients only where
-upstream defines them (features of grouping_operation / gather_operation / three_interpolate)."""
+upstream defines them (features of grouping_operation / gather_operation / three_interpolate).
+
+furthest_point_sample takes every shape upstream's does (N up to 4 194 304, npoint > N included): shapes that fit one workgroup's
+LDS run gad_furthest_point_sampling, every other shape gad_fps_tiled -- same indices.  The fused set-abstraction path
+(sa_function / engine.Geometry, i.e. PointnetSAModule[MSG] with bn=True, use_xyz=True and features) does NOT route: it calls the
+LDS kernel and keeps its refusals (N > 16384, npoint > N, 3N + npoint beyond 160 KiB of LDS)."""
 import torch
 import torch.nn as nn
 
@@ -13,14 +18,27 @@ def _check(*tensors):
     hip.require_cuda(*tensors)
 
 
+def fps_fits_one_workgroup(N, M):
+    """the shapes gad_furthest_point_sampling accepts (include/gaddpg.h: cloud + exchange slots + picks in 160 KiB of LDS)"""
+    return N <= 16384 and M <= N and (((N * 3 + 3) & ~3) + 64 + M) * 4 <= 160 * 1024
+
+
 def furthest_point_sample(xyz, npoint):
     """xyz (B,N,3) float32 CUDA contiguous -> (B,npoint) int32."""
     _check(xyz)
     if xyz.dtype != torch.float32:
         raise RuntimeError("xyz must be a float tensor")
     B, N, _ = xyz.shape
-    idx = torch.empty(B, npoint, dtype=torch.int32, device=xyz.device)
-    hip.call("gad_furthest_point_sampling", xyz, B, N, int(npoint), idx, None)
+    M = int(npoint)
+    idx = torch.empty(B, M, dtype=torch.int32, device=xyz.device)
+    if fps_fits_one_workgroup(N, M):
+        hip.call("gad_furthest_point_sampling", xyz, B, N, M, idx, None)
+        return idx
+    nbytes = hip.lib().gad_fps_tiled_workspace_bytes(B, N, M, 0)
+    if nbytes < 0:
+        hip.check(int(nbytes), "gad_fps_tiled_workspace_bytes")
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=xyz.device)
+    hip.call("gad_fps_tiled", xyz, B, N, M, 0, idx, None, workspace)
     return idx
 
 

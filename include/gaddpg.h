@@ -56,7 +56,9 @@ int gad_abi_version(void);                 /* bumped on any signature change or 
                                             * is GAD_OK without a launch, a negative one, a row pitch < C or a count < 1 is
                                             * GAD_ERR_SHAPE): calls that were valid before behave as before; gad_three_nn,
                                             * gad_three_interpolate, gad_three_interpolate_grad (additive: section A now
-                                            * covers all nine operators of pointnet2_ops._ext)                          */
+                                            * covers all nine operators of pointnet2_ops._ext); gad_fps_tiled and
+                                            * gad_fps_tiled_workspace_bytes (additive: furthest point sampling without
+                                            * the size limits of gad_furthest_point_sampling)                           */
 /* diagnostics: which kernel family the last gad_gemm_fwd / _dx / _dw / _bwd call routed to ("gemm_fwd(stream)",
  * "gemm_dx(wide)", "gemm_bwd(stream)", "gemm_dw" = generic tile kernel, ...); bench.py labels its per-kernel table
  * with it instead of restating the routing rules.                                                  */
@@ -131,6 +133,27 @@ int gad_grid_rows_hint(const int32_t* rows_host, void* stream);
  * does.  new_xyz (B,M,3) is optional (fused gather_operation of the xyz rows).    */
 int gad_furthest_point_sampling(const float* xyz, int B, int N, int M, int32_t* idx,
                                 float* new_xyz /*nullable*/, void* stream);
+/* Limits of the entry point above: one workgroup keeps its whole cloud and the M picks in LDS, so N <= 16384, M <= N and
+ * (3N + M + 64) * 4 bytes <= 160 KiB are required (GAD_ERR_SHAPE otherwise).  The fused set-abstraction path (engine.Geometry /
+ * sa_function of the Python package) calls it and inherits the limits.  Upstream's operator has none of them (npoint > N included):
+ *
+ * gad_fps_tiled: the same operator -- same start index, skip rule, distance evaluation order and tie rule with
+ * tie_bs = pow2 <= min(N, 512), hence the same indices bit for bit -- for any 1 <= N <= 4 194 304 and any M >= 0, M > N included
+ * (once every remaining distance is 0 the tie rule alone picks the index, as it does upstream; a cloud whose points are all
+ * skipped gives index 0 throughout).  Larger N is GAD_ERR_SHAPE: the arg-max key holds 9 tie bits + 22 index bits.
+ * A cloud is cut into `groups` contiguous slices of ceil(N / groups) points, one workgroup each (grid = groups x B);
+ * 0 <= groups <= N, 0 = chosen by the library (one slice per 1024 points); the result does not depend on it.  The call enqueues
+ * M + 1 launches on `stream` -- one per pick, ordered by the stream alone: no workgroup waits for another inside a launch -- and
+ * returns without synchronising.  B == 0 or M == 0: GAD_OK without a launch (workspace may then be NULL).
+ * Workspace contract: `workspace` is caller-allocated DEVICE memory of at least gad_fps_tiled_workspace_bytes(B, N, M, groups)
+ * bytes, 8-byte aligned, uninitialised on entry, owned by the call until its launches have run on `stream` (two calls in flight
+ * on different streams need two workspaces), free to reuse afterwards.  It holds the running minimum distances (B,N) f32
+ * -- upstream's `temp` tensor -- and one 64-bit arg-max slot per cloud and pick; the size is >= B*N*4 + B*M*8 and grows with
+ * N and M.  gad_fps_tiled_workspace_bytes applies the shape checks of gad_fps_tiled and returns a negative gad_status
+ * (message through gad_last_error) where that would refuse.                                                                  */
+long long gad_fps_tiled_workspace_bytes(int B, int N, int M, int groups);
+int gad_fps_tiled(const float* xyz, int B, int N, int M, int groups, int32_t* idx, float* new_xyz /*nullable*/,
+                  void* workspace, void* stream);
 
 /* gather_points(points (B,C,N), idx (B,M)) -> out (B,C,M);  _grad scatters back (zero-fills).  */
 int gad_gather_points(const float* points, const int32_t* idx, int B, int C, int N, int M,
