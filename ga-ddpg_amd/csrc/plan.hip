@@ -85,6 +85,7 @@ const std::vector<reg_entry>& registry() {
         GAD_PLAN_ENTRY(gad_gather_points)
         GAD_PLAN_ENTRY(gad_gather_points_grad)
         GAD_PLAN_ENTRY(gad_ball_query)
+        GAD_PLAN_ENTRY(gad_ball_query_grid)
         GAD_PLAN_ENTRY(gad_group_points)
         GAD_PLAN_ENTRY(gad_group_points_grad)
         GAD_PLAN_ENTRY(gad_three_nn)

@@ -149,7 +149,8 @@ def lib():
 EXPORTS = (
     "gad_abi_version", "gad_last_kernel", "gad_last_error", "gad_set_option", "gad_timing_slot", "gad_stream_priority", "gad_wall_clock_khz", "gad_grid_rows_hint", "gad_bn_running_update", "gad_replay_gather", "gad_replay_gather_multi", "gad_replay_relabel_goals", "gad_zero_buffers", "gad_furthest_point_sampling", "gad_gather_points",
     "gad_fps_tiled_workspace_bytes", "gad_fps_tiled",
-    "gad_gather_points_grad", "gad_ball_query", "gad_group_points", "gad_group_points_grad",
+    "gad_gather_points_grad", "gad_ball_query", "gad_ball_query_grid_workspace_bytes", "gad_ball_query_grid",
+    "gad_group_points", "gad_group_points_grad",
     "gad_three_nn", "gad_three_interpolate", "gad_three_interpolate_grad",
     "gad_query_and_group", "gad_prep_points", "gad_rows_from_ball_query", "gad_rows_group_all",
     "gad_gemm_fwd", "gad_bn_finalize", "gad_bn_eval_affine", "gad_segment_pool", "gad_pool_finalize", "gad_affine_act", "gad_transpose_batched",
@@ -162,18 +163,29 @@ EXPORTS = (
     "gad_plan_entry_count", "gad_plan_entry_name")
 
 
-# argument types of the feature-propagation and tiled-sampling entry points (include/gaddpg.h section A), set when the library
+# argument types of the feature-propagation, tiled-sampling and grid-search entry points (include/gaddpg.h section A), set when the library
 # loads: ctypes then refuses a call whose argument count or kinds do not match
 _SIGNATURES = {
     "gad_fps_tiled_workspace_bytes": [C.c_int, C.c_int, C.c_int, C.c_int],
     "gad_fps_tiled": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp],
+    "gad_ball_query_grid_workspace_bytes": [C.c_int, C.c_int, C.c_int, C.c_int],
+    "gad_ball_query_grid": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, _vp, _vp, _vp],
     "gad_three_nn": [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp],
     "gad_three_interpolate": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
     "gad_three_interpolate_grad": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
 }
 
 
-_RESTYPES = {"gad_fps_tiled_workspace_bytes": C.c_longlong}       # every other entry point returns an int status
+# every other entry point returns an int status
+_RESTYPES = {"gad_fps_tiled_workspace_bytes": C.c_longlong, "gad_ball_query_grid_workspace_bytes": C.c_longlong}
+
+
+def workspace(name, device, *shape):
+    """uninitialised device memory of the size entry point `name`_workspace_bytes(*shape) asks for (raises where it refuses)"""
+    nbytes = getattr(lib(), name + "_workspace_bytes")(*shape)
+    if nbytes < 0:
+        check(int(nbytes), name + "_workspace_bytes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
 class Ptr(int):

@@ -46,10 +46,14 @@ class PointnetSAModuleMSG(nn.Module):
     max-pool over the neighbourhood.  Same results as upstream's module; the padded (B, C, npoint, nsample) tensor is materialised,
     as it is there (no shipped GA-DDPG configuration builds these forms).
 
-    npoint and cloud size: the generic composition samples through pointnet2_utils.furthest_point_sample and takes what upstream
-    takes, npoint > N and clouds beyond one workgroup's LDS included.  The fused path calls gad_furthest_point_sampling directly
-    and keeps its refusals (include/gaddpg.h): N <= 16384, npoint <= N, (3N + npoint + 64) * 4 bytes within 160 KiB -- it raises
-    RuntimeError otherwise."""
+    npoint and cloud size: both paths take what upstream takes, npoint > N and clouds beyond one workgroup's LDS included, by the
+    routing predicates of pointnet2_utils (fps_fits_one_workgroup, ball_query_uses_grid): shapes the LDS kernels hold keep
+    gad_furthest_point_sampling and gad_ball_query, every other shape runs gad_fps_tiled and, from 262 144 points (or beyond 4096
+    with library option "bq_grid" = 2), gad_ball_query_grid -- same centroids and neighbourhoods.  With several scales the fused path runs once per scale and each
+    pass repeats the furthest point sampling (npoint + 1 launches per scale for a cloud gad_fps_tiled takes); sharing it between
+    the scales is left undone.  The only refusal left on the fused path is a shape whose rows overflow the layer kernels' 32-bit
+    indexing (RuntimeError with the sizes).  engine.Geometry -- the update step and feature_forward, not these modules -- keeps
+    the LDS sampler and its refusals (include/gaddpg.h: N <= 16384, npoint <= N, (3N + npoint + 64) * 4 bytes within 160 KiB)."""
 
     def __init__(self, npoint, radii, nsamples, mlps, bn=True, use_xyz=True):
         super().__init__()

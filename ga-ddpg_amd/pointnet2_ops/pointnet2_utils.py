@@ -5,9 +5,13 @@ dtypes (indices are int32), contiguity / device checks raising RuntimeError, gra
 upstream defines them (features of grouping_operation / gather_operation / three_interpolate).
 
 furthest_point_sample takes every shape upstream's does (N up to 4 194 304, npoint > N included): shapes that fit one workgroup's
-LDS run gad_furthest_point_sampling, every other shape gad_fps_tiled -- same indices.  The fused set-abstraction path
-(sa_function / engine.Geometry, i.e. PointnetSAModule[MSG] with bn=True, use_xyz=True and features) does NOT route: it calls the
-LDS kernel and keeps its refusals (N > 16384, npoint > N, 3N + npoint beyond 160 KiB of LDS)."""
+LDS run gad_furthest_point_sampling, every other shape gad_fps_tiled -- same indices.  ball_query sends clouds of 262 144 points
+and more (ball_query_uses_grid: the sizes at which it was measured faster, profiles/ball_query_grid.txt) to gad_ball_query_grid, a
+uniform grid in global memory, and every other shape to gad_ball_query -- same indices; library option "bq_grid" = 0 keeps the scan
+for all of them, 2 sends every cloud beyond 4096 points to the grid.  The fused set-abstraction modules (sa_function, i.e.
+PointnetSAModule[MSG] with bn=True, use_xyz=True and features) route by the same two predicates.  What is left of the LDS
+kernels' refusals (N > 16384, npoint > N, 3N + npoint beyond 160 KiB of LDS) is engine.Geometry: the update step and
+feature_forward call gad_furthest_point_sampling directly."""
 import torch
 import torch.nn as nn
 
@@ -23,6 +27,24 @@ def fps_fits_one_workgroup(N, M):
     return N <= 16384 and M <= N and (((N * 3 + 3) & ~3) + 64 + M) * 4 <= 160 * 1024
 
 
+BQ_LDS_MAX_N = 4096       # gad_ball_query keeps clouds up to here in one workgroup's LDS: never sent to the grid
+# smallest cloud sent to gad_ball_query_grid by default.  profiles/ball_query_grid.txt (MI355X, B = 1, box-surface clouds): with
+# balls of about 16 points -- fewer than nsample, the first-stage regime, where the scan walks the whole cloud -- the grid takes
+# 0.11-0.37 of the scan's time at N = 4097 / 8192 (it loses: building it costs 140-200 us), 0.85-0.92 at N = 65536 with up to 4096
+# centroids, and wins 1.7-4.3 x at N = 262144 and 3.2-6.2 x at N = 1048576 for every centroid count measured (spread of a row < 3 %).
+# With balls of about 300 points the scan stops after nsample hits and stays faster at nearly every size: set "bq_grid" = 0 there.
+BQ_GRID_MIN_N = 262144
+
+
+def ball_query_uses_grid(N):
+    """the shapes ball_query and the fused set-abstraction path send to gad_ball_query_grid.  Library option "bq_grid": 1 (default)
+    = clouds of BQ_GRID_MIN_N points and more, 0 = none, 2 = every cloud beyond the BQ_LDS_MAX_N points of the LDS kernels"""
+    mode = hip.get_option("bq_grid")
+    if mode == 0 or N <= BQ_LDS_MAX_N:
+        return False
+    return mode >= 2 or N >= BQ_GRID_MIN_N
+
+
 def furthest_point_sample(xyz, npoint):
     """xyz (B,N,3) float32 CUDA contiguous -> (B,npoint) int32."""
     _check(xyz)
@@ -34,11 +56,7 @@ def furthest_point_sample(xyz, npoint):
     if fps_fits_one_workgroup(N, M):
         hip.call("gad_furthest_point_sampling", xyz, B, N, M, idx, None)
         return idx
-    nbytes = hip.lib().gad_fps_tiled_workspace_bytes(B, N, M, 0)
-    if nbytes < 0:
-        hip.check(int(nbytes), "gad_fps_tiled_workspace_bytes")
-    workspace = torch.empty(nbytes, dtype=torch.uint8, device=xyz.device)
-    hip.call("gad_fps_tiled", xyz, B, N, M, 0, idx, None, workspace)
+    hip.call("gad_fps_tiled", xyz, B, N, M, 0, idx, None, hip.workspace("gad_fps_tiled", xyz.device, B, N, M, 0))
     return idx
 
 
@@ -74,6 +92,10 @@ def ball_query(radius, nsample, xyz, new_xyz):
     B, N, _ = xyz.shape
     M = new_xyz.shape[1]
     idx = torch.empty(B, M, nsample, dtype=torch.int32, device=xyz.device)
+    if ball_query_uses_grid(N):
+        hip.call("gad_ball_query_grid", new_xyz, xyz, B, N, M, float(radius), int(nsample), idx, None,
+                 hip.workspace("gad_ball_query_grid", xyz.device, B, N, M, int(nsample)))
+        return idx
     hip.call("gad_ball_query", new_xyz, xyz, B, N, M, float(radius), int(nsample), idx, None)
     return idx
 

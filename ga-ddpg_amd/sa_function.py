@@ -1,6 +1,9 @@
 """Stand-alone evaluation of one `PointnetSAModule` through the fused libgaddpg path
 (pointnet2_ops.pointnet2_modules.PointnetSAModule.forward): FPS -> ball query -> de-duplicated rows
 -> gather + 3 x (1x1 conv, BatchNorm, ReLU) as FP32-MFMA GEMMs -> segment max-pool.
+Cloud size: shapes the one-workgroup kernels hold keep their calls (gad_furthest_point_sampling, gad_ball_query); every other
+shape takes gad_fps_tiled (npoint + 1 launches) and, where pointnet2_utils.ball_query_uses_grid holds, gad_ball_query_grid -- the
+routing predicates of pointnet2_utils, evaluated when the _StageRun is built; its workspaces belong to it.
 
 Differentiable: the forward is wrapped in a torch.autograd.Function whose backward drives the same
 dX / dW kernels as the fused update step (BatchNorm-backward with weighted statistics, max-pool routing
@@ -16,6 +19,7 @@ import torch
 
 from . import engine, hip
 from .engine import BN_EPS, BN_MOMENTUM, FlatNet, MatSpec, Plan, _dz, _fwd_args, _ptr
+from .pointnet2_ops import pointnet2_utils as pu
 
 
 class _StageNet(object):
@@ -68,6 +72,13 @@ class _StageRun(object):
         self.M, self.S = M, S
         G = B * M
         cap = G * S
+        # the row lists and layer kernels hold point and row numbers, and element offsets built from them, in int32: point rows of
+        # c_pad floats, activation rows of up to max(n_out) floats
+        widest = max(m.n_out for m in net.mats)
+        if B * N * max(net.c_pad, 3) >= 2 ** 31 or cap * widest >= 2 ** 31:
+            raise RuntimeError("PointnetSAModule: B=%d N=%d npoint=%d nsample=%d needs %d point rows of %d floats and %d activation "
+                               "rows of %d floats; the fused path indexes the elements of both in 32 bits"
+                               % (B, N, M, S, B * N, net.c_pad, cap, widest))
         self.xyz = torch.empty(B, N, 3, **f32)
         self.feat = torch.zeros(B * N, net.c_pad, **f32)      # padding columns stay zero
         self.new_xyz = torch.empty(B, M, 3, **f32)
@@ -97,6 +108,7 @@ class _StageRun(object):
         self.key = torch.zeros(G, c_out, dtype=torch.int64, device=device) if self.fused_pool else None
         # raw value of every arg-max row (the backward's BatchNorm sums read it instead of gathering z[argmax])
         self.zmax = torch.empty(G, c_out, **f32) if (self.fused_pool and with_backward) else None
+        self.workspaces = {}                                  # entry point -> device workspace (shapes beyond the LDS kernels)
         self.plans = {t: self._plan(net, mod, t) for t in (True, False)}
         self.bwd = None
         if with_backward:
@@ -107,6 +119,12 @@ class _StageRun(object):
             self.dfeat = torch.zeros(B * N, net.c_pad, **f32)
             self.grad = torch.zeros(net.flat.n, **f32)        # this call's parameter gradients (master layout)
             self.bwd = self._plan_backward(net)
+
+    def _workspace(self, name, *shape):
+        ws = self.workspaces.get(name)
+        if ws is None:
+            ws = self.workspaces[name] = hip.workspace(name, self.xyz.device, *shape)
+        return ws
 
     def _input(self, net, mod, l):
         """gad_gemm_fwd_args fields describing the input of layer l"""
@@ -126,8 +144,17 @@ class _StageRun(object):
         plan = Plan()
         B, N, M, S, r, tot = self.B, self.N, self.M, self.S, self.rows, self.tot
         if not self.group_all:
-            plan.call("gad_furthest_point_sampling", self.xyz, B, N, M, self.fps, self.new_xyz)
-            plan.call("gad_ball_query", self.new_xyz, self.xyz, B, N, M, float(mod.radius), S, self.idx, self.cnt)
+            # shapes beyond the LDS kernels take the entry points of the facade (pointnet2_utils: same predicates, same indices);
+            # their workspaces belong to this run -- its forward is one stream, so one per entry point serves both plans
+            if pu.fps_fits_one_workgroup(N, M):
+                plan.call("gad_furthest_point_sampling", self.xyz, B, N, M, self.fps, self.new_xyz)
+            else:
+                plan.call("gad_fps_tiled", self.xyz, B, N, M, 0, self.fps, self.new_xyz, self._workspace("gad_fps_tiled", B, N, M, 0))
+            if pu.ball_query_uses_grid(N):
+                plan.call("gad_ball_query_grid", self.new_xyz, self.xyz, B, N, M, float(mod.radius), S, self.idx, self.cnt,
+                          self._workspace("gad_ball_query_grid", B, N, M, S))
+            else:
+                plan.call("gad_ball_query", self.new_xyz, self.xyz, B, N, M, float(mod.radius), S, self.idx, self.cnt)
             plan.call("gad_rows_from_ball_query", self.idx, self.cnt, B * M, M, N, S, r["off"], r["pt"], r["grp"],
                       r["w"], r["n"])
         plan.zero(self.stats)

@@ -58,13 +58,18 @@ int gad_abi_version(void);                 /* bumped on any signature change or 
                                             * gad_three_interpolate, gad_three_interpolate_grad (additive: section A now
                                             * covers all nine operators of pointnet2_ops._ext); gad_fps_tiled and
                                             * gad_fps_tiled_workspace_bytes (additive: furthest point sampling without
-                                            * the size limits of gad_furthest_point_sampling)                           */
+                                            * the size limits of gad_furthest_point_sampling); gad_ball_query_grid and
+                                            * gad_ball_query_grid_workspace_bytes, option "bq_grid" (additive: the radius
+                                            * search through a uniform grid in global memory)                           */
 /* diagnostics: which kernel family the last gad_gemm_fwd / _dx / _dw / _bwd call routed to ("gemm_fwd(stream)",
  * "gemm_dx(wide)", "gemm_bwd(stream)", "gemm_dw" = generic tile kernel, ...); bench.py labels its per-kernel table
  * with it instead of restating the routing rules.                                                  */
 const char* gad_last_kernel(void);
 const char* gad_last_error(void);          /* thread-local description of the last <0   */
-/* Kernel-selection switches for A/B diagnostics (defaults in brackets).  "fwd_stream" [1]: route the wide and
+/* Kernel-selection switches for A/B diagnostics (defaults in brackets).  "bq_cells" [1]: the LDS cell list of gad_ball_query /
+ * gad_query_and_group (0: the tile scan); "bq_grid" [1]: 0 = gad_ball_query_grid runs the scan kernel and the Python routes call
+ * gad_ball_query instead of it; 2 = the Python routes send every cloud beyond 4096 points to it instead of those from 262 144
+ * points, where it was measured faster (profiles/ball_query_grid.txt) -- same results whatever the value.  "fwd_stream" [1]: route the wide and
  * shallow SA1 forward layers to the streaming kernel instead of the tiled one; "dx_stream" [1]: the same for their dX; "fwd_skinny" / "dx_skinny" / "dw_skinny" [1]: route
  * the small-M (<= 1024 rows) forward / dX / dW layers to the split-K kernels; "skinny_nw" [8]: wavefronts per workgroup of
  * those kernels (8, or 4 = the small-footprint instantiation: A/B in profiles/r05_skinny_footprint.txt); "fwd_stream_wgs" [256] /
@@ -134,8 +139,9 @@ int gad_grid_rows_hint(const int32_t* rows_host, void* stream);
 int gad_furthest_point_sampling(const float* xyz, int B, int N, int M, int32_t* idx,
                                 float* new_xyz /*nullable*/, void* stream);
 /* Limits of the entry point above: one workgroup keeps its whole cloud and the M picks in LDS, so N <= 16384, M <= N and
- * (3N + M + 64) * 4 bytes <= 160 KiB are required (GAD_ERR_SHAPE otherwise).  The fused set-abstraction path (engine.Geometry /
- * sa_function of the Python package) calls it and inherits the limits.  Upstream's operator has none of them (npoint > N included):
+ * (3N + M + 64) * 4 bytes <= 160 KiB are required (GAD_ERR_SHAPE otherwise).  engine.Geometry of the Python package (the update
+ * step and feature_forward) calls it and inherits the limits; the fused set-abstraction modules (sa_function) call gad_fps_tiled
+ * for a shape outside them.  Upstream's operator has none of them (npoint > N included):
  *
  * gad_fps_tiled: the same operator -- same start index, skip rule, distance evaluation order and tie rule with
  * tie_bs = pow2 <= min(N, 512), hence the same indices bit for bit -- for any 1 <= N <= 4 194 304 and any M >= 0, M > N included
@@ -166,6 +172,34 @@ int gad_gather_points_grad(const float* grad_out, const int32_t* idx, int B, int
  * cnt (B,M) (optional) receives the number of distinct hits kept (<= nsample).                  */
 int gad_ball_query(const float* new_xyz, const float* xyz, int B, int N, int M, float radius,
                    int nsample, int32_t* idx, int32_t* cnt /*nullable*/, void* stream);
+/* Up to 4096 points gad_ball_query keeps the cloud in one workgroup's LDS (a cell list for nsample <= 128, a tile scan for
+ * nsample <= 256); every other shape is the scan: one wavefront per centroid walks the cloud from global memory until nsample
+ * hits are found -- all N points where the ball holds fewer.
+ *
+ * gad_ball_query_grid: the same operator, idx and cnt equal to gad_ball_query's bit for bit for every input -- the predicate is
+ * d2 = ((dx*dx) + (dy*dy)) + (dz*dz) < radius * radius, every operation rounded in float32, and it decides every candidate --
+ * through a uniform grid per cloud in global memory: any N >= 1 and nsample >= 1; it pays for its seven launches from a few
+ * hundred thousand points where balls hold fewer than nsample points (profiles/ball_query_grid.txt).  Each cloud's finite
+ * points give its bounding box; the grid's resolution is chosen on the device from that box (cell edge >= 1.002 x radius, at
+ * most 1024 cells per axis and min(max(N / 4, 64), 65536) per cloud -- a budget the host derives from N alone); a stable counting
+ * sort lists the cloud by cell, indices ascending inside a cell; a wavefront per centroid tests the 27 cells around the
+ * centroid's and places the nsample smallest hit indices in ascending order.  A centroid outside the box is clamped to a border
+ * cell; a point or centroid with a non-finite coordinate is never a hit (such a centroid: zeros, cnt 0); flat clouds and clouds
+ * of equal points are legal.  A centroid with more than 512 hits among its candidates is redone by the scan inside the same
+ * launch.  radius <= 0, NaN or >= 1e18 (and option "bq_grid" = 0): the call runs gad_ball_query's scan kernel.
+ * The call enqueues seven launches on `stream` (bounds, grid set-up, per-slice stable ranks, slice prefix, cell prefix, scatter,
+ * query) ordered by the stream alone -- no workgroup waits for another inside a launch, no host synchronisation, no allocation.
+ * The sorted cloud does not depend on scheduling: the only atomics are integer adds into counters owned by one wavefront.
+ * Workspace contract as for gad_fps_tiled: caller-allocated DEVICE memory of at least
+ * gad_ball_query_grid_workspace_bytes(B, N, M, nsample) bytes, 8-byte aligned, uninitialised on entry, owned by the call until
+ * its launches have run on `stream`, free to reuse afterwards (also for another shape it is large enough for).  The size grows
+ * with N only (about 24 bytes per point plus the cell tables, at most 16 MiB per cloud).  B * M == 0: GAD_OK without a launch
+ * (workspace may then be NULL).  GAD_ERR_NULL / GAD_ERR_SHAPE: null pointers, a negative size, N < 1, nsample < 1, a misaligned
+ * workspace, 3 * N or B * N beyond 2^31, B * M beyond 2^26 or B beyond 65535; gad_ball_query_grid_workspace_bytes applies the
+ * same shape checks and returns the negative gad_status.  Measured against the scan: profiles/ball_query_grid.txt.           */
+long long gad_ball_query_grid_workspace_bytes(int B, int N, int M, int nsample);
+int gad_ball_query_grid(const float* new_xyz, const float* xyz, int B, int N, int M, float radius, int nsample, int32_t* idx,
+                        int32_t* cnt /*nullable*/, void* workspace, void* stream);
 
 /* group_points(points (B,C,N), idx (B,M,S)) -> out (B,C,M,S);  _grad: atomic scatter-add into
  * grad_points (B,C,N), which the call zero-fills first (upstream torch::zeros + atomicAdd).      */
