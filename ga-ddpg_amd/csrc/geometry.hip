@@ -1077,9 +1077,11 @@ __global__ __launch_bounds__(BQC_THREADS) void ball_query_cells_kernel(const flo
 
 static int g_opt_bq_cells = 1;
 static int g_opt_bq_grid = 1;     // 0: gad_ball_query_grid runs the scan kernel (A/B; the Python routes then call gad_ball_query)
+static int g_opt_tnn_grid = 1;    // 0: gad_three_nn_grid runs three_nn_kernel (A/B; the Python route then calls gad_three_nn)
 void gad_geometry_set_option(const char* name, int value, int* found) {
     if (!strcmp(name, "bq_cells")) { g_opt_bq_cells = value; *found = 1; }
     if (!strcmp(name, "bq_grid")) { g_opt_bq_grid = value; *found = 1; }
+    if (!strcmp(name, "tnn_grid")) { g_opt_tnn_grid = value; *found = 1; }
     if (!strcmp(name, "fps_cfg")) { g_opt_fps_cfg = value; *found = 1; }
 }
 static bool bq_use_cells(int N, int nsample, float radius) {
@@ -1708,6 +1710,324 @@ extern "C" int gad_three_nn(const float* unknown, const float* known, int B, int
     GAD_REQUIRE((long long)B * tiles < (1ll << 31), GAD_ERR_SHAPE, "three_nn: B * n too large");
     hipLaunchKernelGGL(three_nn_kernel, dim3(B * tiles), dim3(256), 0, (hipStream_t)stream, unknown, known, n, m, tiles, dist2, idx);
     GAD_CHECK_LAUNCH("three_nn");
+    return GAD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// three_nn of large clouds: the uniform grid of gad_ball_query_grid over the KNOWN points, searched ring by ring
+// ------------------------------------------------------------------------------------------------
+// three_nn_kernel evaluates all n * m distances.  Here each cloud's known points are sorted once into a uniform grid -- the
+// bounds / count / slices / scan / scatter launches of gad_ball_query_grid, unchanged -- and a wavefront per query tests the
+// 3 x 3 x 3 cells around the query's (clamped) cell, then the shells of cells around that block, until no unexamined point can
+// enter the answer.  Seven launches on the caller's stream, no host synchronisation, nothing sized by the data.
+//   setup    there is no radius: one wavefront per cloud picks the cell edge from the box of the finite points and the cell
+//            budget the host derives from m alone (min(max(m / 4, 64), 65536), the ball query's rule: about four points per
+//            cell of a cloud that fills its box).  The first edge is the one at which box volume / edge^3 (area / edge^2 and
+//            length / edge where one or two extents are zero) equals the budget, at least extent / BQG_GMAX; it is coarsened by
+//            1.1 x per try until the cells, counted as the cell function counts them, fit.  An axis of zero extent gets one
+//            cell, a box whose extent overflows ends in one cell (every point a candidate of the first block: still exact).
+//   query    a candidate is the 64-bit key (bits of d) << 32 | index: d = gad_sqdist >= +0 in the pinned order, so unsigned
+//            order of the keys IS the total order (d, index), and every key of a d that is +inf or NaN is >= the empty slot's
+//            key (+inf, 0) and fails the strict < of the insertion.  Each lane keeps the three smallest keys of the candidates
+//            it saw, a wavefront merge gives the three smallest of all: the result of three_nn_kernel's sequential strict-<
+//            insertion, in whatever order the candidates are visited (every cell is visited once: no key twice).
+// Stop test.  After ring r the examined block is cells [i - r, i + r] of every axis, cut to the grid.  An unexamined point lies
+// beyond a face of the block that is not a border of the grid (border cells hold everything beyond them: the cell function is
+// monotone and clamped).  With t = (p - lo) * inv in exact arithmetic, a point beyond the low (high) face of an axis has
+// t < i - r (t >= i + r + 1) and the query t >= f (<= f), f its computed cell coordinate: along that axis they are `face`
+// = f - (i - r) (or i + r + 1 - f) cells apart.  Along each OTHER axis any point of the cloud has 0 <= t < n, n the cells of the
+// axis, so it is at least `out` = max(0, -f, f - n) cells from the query: what a query outside the box gains (without it such
+// a query, clamped to a border cell, would never see a bound as large as its distance to the box and would always fall back).
+// A point beyond a face is therefore at least sqrt(face^2 + out'^2 + out''^2) cells away, and the bound is the least of that
+// over the non-border faces.  Rounding: f is clamped to [-2048, 3072] first -- towards the box: every term only shrinks -- so
+// the computed (p - lo) * inv (two roundings, 1.2e-7 relative) is off by < 3.7e-4 cells for the query and, at <= BQG_GMAX
+// cells per axis, < 1.3e-4 for a point (the same holds for the extent, whose computed cell count is < n), and a difference
+// of f and an integer by < 1.9e-4 more (one rounding at <= 3072): 6.9e-4 cells in all, TNN_CELL_SLACK = 1e-3 is taken off every
+// term.  With c2 the resulting sum of squares the point is at least L = sqrt(c2) / inv away, and its d, five roundings of
+// non-negative terms, is >= L * L * (1 - 3e-7).  The bound used is L * L * 0.99999 (1e-5 covers the 3e-7 and the roundings of
+// forming c2, the root and L * L), ignored below 1e-30, where squares leave the normal range; an L * L that overflows stands
+// for a bound no float reaches.  The search stops when the third-best d is STRICTLY below the bound -- a point at equal d
+// and lower index would have to win -- or when the block covers the grid (fewer than three finite points, m < 3).  Every slack
+// makes the bound smaller: one ring too many, never one too few.
+// A query with a non-finite coordinate has no finite d: (+inf, 0) x 3 without a search.  A query unresolved after TNN_RINGS
+// rings (far outside the box, in a large void) is redone by the wavefront walking all m known points: exact, only slower.
+#define TNN_RINGS 3                                // (2 * 3 + 1)^2 = 49 (y, z) rows of a shell: one lane each
+#define TNN_CELL_SLACK 1.0e-3f
+#define TNN_INF_KEY 0x7f80000000000000ull          // (+inf, index 0): an unfilled slot
+#define TNN_WAVES_TARGET 65536                     // wavefronts of the query launch where B * n allows (each takes a run of queries)
+
+typedef unsigned long long tnn_key;
+
+// (k0, k1, k2) <- the three smallest of {k0 <= k1 <= k2, k}: compare-exchanges, no branch (and no slot picked by an index)
+__device__ __forceinline__ void tnn_insert(tnn_key k, tnn_key& k0, tnn_key& k1, tnn_key& k2) {
+    tnn_key t = k0 < k ? k : k0;
+    k0 = k0 < k ? k0 : k;
+    const tnn_key u = k1 < t ? t : k1;
+    k1 = k1 < t ? k1 : t;
+    k2 = k2 < u ? k2 : u;
+}
+__device__ __forceinline__ tnn_key tnn_make_key(float d, int k) { return ((tnn_key)__float_as_uint(d) << 32) | (unsigned)k; }
+
+__device__ __forceinline__ tnn_key tnn_wave_min(tnn_key v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
+        const tnn_key w = ((tnn_key)hi << 32) | lo;
+        v = w < v ? w : v;
+    }
+    // (every lane holds the minimum: say so to the compiler, the branches on it are then scalar)
+    return ((tnn_key)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+}
+// the three smallest keys over the lanes' lists (which stay as they are); every filled key is unique: one lane pops per round
+__device__ __forceinline__ void tnn_wave_best3(tnn_key a0, tnn_key a1, tnn_key a2, tnn_key& g0, tnn_key& g1, tnn_key& g2) {
+    g0 = tnn_wave_min(a0);
+    if (a0 == g0) { a0 = a1; a1 = a2; a2 = TNN_INF_KEY; }
+    g1 = tnn_wave_min(a0);
+    if (a0 == g1) { a0 = a1; a1 = a2; }
+    g2 = tnn_wave_min(a0);
+}
+
+// every lane brings one run [rs, rs + rl) of the sorted cloud (rl = 0: none); the wavefront walks the runs' points 64 at a time
+__device__ __forceinline__ void tnn_scan_runs(const float4* __restrict__ sp, int m, int rs, int rl, int lane, float ux, float uy,
+                                              float uz, tnn_key& k0, tnn_key& k1, tnn_key& k2) {
+    int incl = rl;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+    }
+    const int T = min(__builtin_amdgcn_readfirstlane(__shfl(incl, 63, 64)), m);   // (the runs are disjoint: at most m points)
+    const int off = rs - (incl - rl);                             // candidate t of this lane's run is sorted[off + t]
+    for (int t0 = 0; t0 < T; t0 += 64) {                          // wave-uniform
+        const int t = t0 + lane;
+        int j = 0;                                                // the run of candidate t: the number of lanes with incl <= t
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) {
+            const int v = __shfl(incl, j + s - 1, 64);
+            if (v <= t) j += s;
+        }
+        const int o = __shfl(off, j, 64);
+        if (t < T) {
+            const float4 v = sp[min(max(o + t, 0), m - 1)];        // (always inside: start[] ascends from 0 to m)
+            tnn_insert(tnn_make_key(gad_sqdist(ux, uy, uz, v.x, v.y, v.z), __float_as_int(v.w)), k0, k1, k2);
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void tnn_setup_kernel(const float* __restrict__ part, int parts, int cells,
+                                                       BqgGrid* __restrict__ hdr, int32_t* __restrict__ stats) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    if (lane < parts) {
+        const float* q = part + ((size_t)b * parts + lane) * 6;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { lo[a] = q[a]; hi[a] = q[3 + a]; }
+    }
+    bqg_wave_minmax(lo, hi);
+    if (lane != 0) return;
+    if (stats) { stats[b * 2] = 0; stats[b * 2 + 1] = 0; }
+    if (!(hi[0] >= lo[0])) {                                      // a cloud without a finite point: one cell at the origin
+#pragma unroll
+        for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0.f;
+    }
+    const float e[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};                 // >= 0; +inf where the box overflows
+    // the edge at which the box, over the axes it extends along, is cut into `cells` cells (roots first: no overflow)
+    float h = 1.f, emax = 0.f;
+    int dims = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (e[a] > 0.f) { ++dims; emax = fmaxf(emax, e[a]); }
+    }
+    if (dims == 3) {
+        h = cbrtf(e[0]) * cbrtf(e[1]) * cbrtf(e[2]) / cbrtf((float)cells);
+    } else if (dims == 2) {
+        h = 1.f;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) h *= e[a] > 0.f ? sqrtf(e[a]) : 1.f;
+        h /= sqrtf((float)cells);
+    } else if (dims == 1) {
+        h = emax / (float)cells;
+    }
+    h = fmaxf(h, emax * (1.0f / (float)BQG_GMAX));
+    if (!(h > 1.0e-30f)) h = 1.0e-30f;                            // (1 / h stays finite)
+    float inv = 0.f;
+    int nx = 1, ny = 1, nz = 1;
+    bool fits = false;
+    for (int it = 0; it < 256 && !fits; ++it) {                   // (the first edge is within 1024 x of one that fits)
+        inv = 1.0f / h;
+        nx = bqg_axis(e[0], inv); ny = bqg_axis(e[1], inv); nz = bqg_axis(e[2], inv);
+        fits = nx <= BQG_GMAX && ny <= BQG_GMAX && nz <= BQG_GMAX && (long long)nx * ny * nz <= (long long)cells;
+        h *= 1.1f;
+    }
+    if (!fits) { nx = ny = nz = 1; inv = 0.f; }                  // (an infinite extent: every point in the one cell)
+    BqgGrid g;
+    g.lox = lo[0]; g.loy = lo[1]; g.loz = lo[2];
+    g.ivx = g.ivy = g.ivz = inv;
+    g.nx = nx; g.ny = ny; g.nz = nz; g.ncells = nx * ny * nz;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) g.reserved_[a] = 0;
+    hdr[b] = g;
+}
+
+// one axis of the stop test, in cells: `face` = the query's distance to the nearest face of the block [i - r, i + r] that is not
+// a border of the grid (+inf: none), `out` = its distance to the box (0 inside); f is the query's computed cell coordinate
+__device__ __forceinline__ void tnn_axis(float f, int i, int r, int n, float& face, float& out) {
+    const float fc = f != f ? 0.f : fminf(fmaxf(f, -2048.f), 3072.f);   // (NaN: an overflowed difference times inv = 0, one cell)
+    face = __builtin_huge_valf();
+    if (i - r > 0) face = fminf(face, fc - (float)(i - r));
+    if (i + r < n - 1) face = fminf(face, (float)(i + r + 1) - fc);
+    out = fmaxf(0.f, fmaxf(-fc, fc - (float)n));
+}
+__device__ __forceinline__ float tnn_sq_less_slack(float cells) {
+    const float v = fmaxf(cells - TNN_CELL_SLACK, 0.f);
+    return v * v;
+}
+
+__global__ __launch_bounds__(256) void tnn_query_kernel(const float* __restrict__ unknown, const float* __restrict__ known, int n,
+                                                        int m, int per_wave, int cells, const BqgGrid* __restrict__ hdr,
+                                                        const int32_t* __restrict__ start, const float4* __restrict__ sorted,
+                                                        float* __restrict__ dist2, int32_t* __restrict__ idx,
+                                                        int32_t* __restrict__ stats) {
+    const int b = blockIdx.y, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const long long q0 = ((long long)blockIdx.x * 4 + wave) * per_wave;
+    if (q0 >= n) return;                                          // wave-uniform; the kernel has no workgroup barrier
+    const int q1 = (int)min((long long)n, q0 + per_wave);
+    const BqgGrid g = hdr[b];
+    const int32_t* st = start + (size_t)b * (cells + 1);
+    const float4* sp = sorted + (size_t)b * m;
+    const float* kb = known + (size_t)b * m * 3;
+    const float inf = __builtin_huge_valf();
+    int from_grid = 0, redone = 0;
+    for (int i = (int)q0; i < q1; ++i) {                          // wave-uniform
+        const size_t o3 = ((size_t)b * n + i) * 3;
+        const float ux = unknown[o3], uy = unknown[o3 + 1], uz = unknown[o3 + 2];
+        tnn_key k0 = TNN_INF_KEY, k1 = TNN_INF_KEY, k2 = TNN_INF_KEY, g0 = TNN_INF_KEY, g1 = TNN_INF_KEY, g2 = TNN_INF_KEY;
+        bool done = !(bqg_finite(ux) && bqg_finite(uy) && bqg_finite(uz));
+        if (!done) {
+            const float fx = (ux - g.lox) * g.ivx, fy = (uy - g.loy) * g.ivy, fz = (uz - g.loz) * g.ivz;
+            const int ix = bqg_cell1(ux, g.lox, g.ivx, g.nx), iy = bqg_cell1(uy, g.loy, g.ivy, g.ny), iz = bqg_cell1(uz, g.loz, g.ivz, g.nz);
+            for (int r = 1; r <= TNN_RINGS && !done; ++r) {
+                // lane = one (y, z) row of the (2r + 1)^2 around the query's: on the shell's y / z faces (and in the first block)
+                // the whole x run of the block, else its two end cells, one per pass
+                const int side = 2 * r + 1;
+                const int dy = lane % side - r, dz = lane / side - r, y = iy + dy, z = iz + dz;
+                const bool row = lane < side * side && y >= 0 && y < g.ny && z >= 0 && z < g.nz;
+                const bool whole = r == 1 || dy == r || dy == -r || dz == r || dz == -r;
+                const int base = row ? (z * g.ny + y) * g.nx : 0;
+                for (int pass = 0; pass < (r == 1 ? 1 : 2); ++pass) {
+                    int x0 = 0, x1 = -1;                          // cells [x0, x1] of the row
+                    if (row && whole && pass == 0) { x0 = max(ix - r, 0); x1 = min(ix + r, g.nx - 1); }
+                    if (row && !whole && pass == 0 && ix - r >= 0) x0 = x1 = ix - r;
+                    if (row && !whole && pass == 1 && ix + r <= g.nx - 1) x0 = x1 = ix + r;
+                    int rs = 0, rl = 0;
+                    if (x1 >= x0) {
+                        rs = st[base + x0];
+                        rl = st[base + x1 + 1] - rs;
+                    }
+                    tnn_scan_runs(sp, m, rs, max(rl, 0), lane, ux, uy, uz, k0, k1, k2);
+                }
+                tnn_wave_best3(k0, k1, k2, g0, g1, g2);
+                float ax, ay, az, ox, oy, oz;
+                tnn_axis(fx, ix, r, g.nx, ax, ox);
+                tnn_axis(fy, iy, r, g.ny, ay, oy);
+                tnn_axis(fz, iz, r, g.nz, az, oz);
+                if (ax == inf && ay == inf && az == inf) {
+                    done = true;                                  // the block covers the grid
+                } else {
+                    const float px = tnn_sq_less_slack(ox), py = tnn_sq_less_slack(oy), pz = tnn_sq_less_slack(oz);
+                    float c2 = inf;                               // the least squared distance, in cells, beyond any such face
+                    if (ax < inf) c2 = fminf(c2, tnn_sq_less_slack(ax) + (py + pz));
+                    if (ay < inf) c2 = fminf(c2, tnn_sq_less_slack(ay) + (px + pz));
+                    if (az < inf) c2 = fminf(c2, tnn_sq_less_slack(az) + (px + py));
+                    const float L = sqrtf(c2) / g.ivx;
+                    const float bound = L * L * 0.99999f;
+                    done = bound > 1.0e-30f && __uint_as_float((unsigned)(g2 >> 32)) < bound;
+                }
+            }
+            if (done) {
+                ++from_grid;
+            } else {                                              // the exhaustive walk, from empty lists
+                ++redone;
+                k0 = k1 = k2 = TNN_INF_KEY;
+#pragma unroll 4
+                for (int k = lane; k < m; k += 64)
+                    tnn_insert(tnn_make_key(gad_sqdist(ux, uy, uz, kb[k * 3 + 0], kb[k * 3 + 1], kb[k * 3 + 2]), k), k0, k1, k2);
+                tnn_wave_best3(k0, k1, k2, g0, g1, g2);
+            }
+        } else {
+            ++from_grid;
+        }
+        if (lane < 3) {
+            const tnn_key k = lane == 0 ? g0 : (lane == 1 ? g1 : g2);
+            dist2[o3 + lane] = __uint_as_float((unsigned)(k >> 32));
+            idx[o3 + lane] = (int32_t)(unsigned)k;
+        }
+    }
+    if (stats && lane == 0) {                                     // at most one add per counter and wavefront
+        if (from_grid) atomicAdd(stats + b * 2, from_grid);
+        if (redone) atomicAdd(stats + b * 2 + 1, redone);
+    }
+}
+
+__global__ __launch_bounds__(64) void tnn_stats_exhaustive_kernel(int B, int n, int32_t* __restrict__ stats) {
+    for (int b = threadIdx.x; b < B; b += 64) { stats[b * 2] = 0; stats[b * 2 + 1] = n; }
+}
+
+// the shape checks of gad_three_nn_grid; the workspace is gad_ball_query_grid's for a cloud of max(m, 1) points
+static int tnn_plan(const char* who, int B, int n, int m, BqgPlan* pl) {
+    GAD_REQUIRE(B >= 0 && n >= 0 && m >= 0, GAD_ERR_SHAPE, "%s: negative size (B=%d n=%d m=%d)", who, B, n, m);
+    GAD_REQUIRE((long long)m * 3 < (1ll << 31) && (long long)B * m < (1ll << 31) && (long long)B * n < (1ll << 31) && B <= 65535,
+                GAD_ERR_SHAPE, "%s: B=%d clouds of n=%d queries and m=%d known points overflows 32-bit indexing (or B > 65535)", who, B, n, m);
+    GAD_REQUIRE(m >= 1 || (long long)B * n == 0, GAD_ERR_SHAPE, "%s: no known point (m=%d) for n=%d queries", who, m, n);
+    return bqg_plan(who, B, std::max(m, 1), 0, 1, pl);
+}
+
+extern "C" long long gad_three_nn_grid_workspace_bytes(int B, int n, int m) {
+    BqgPlan pl;
+    const int rc = tnn_plan("three_nn_grid_workspace_bytes", B, n, m, &pl);
+    return rc != GAD_OK ? rc : pl.total;
+}
+
+extern "C" int gad_three_nn_grid(const float* unknown, const float* known, int B, int n, int m, float* dist2, int32_t* idx,
+                                 int32_t* stats, void* workspace, void* stream) {
+    GAD_REQUIRE(unknown && known && dist2 && idx, GAD_ERR_NULL, "three_nn_grid: null pointer (unknown / known / dist2 / idx)");
+    BqgPlan pl;
+    const int rc = tnn_plan("three_nn_grid", B, n, m, &pl);
+    if (rc != GAD_OK) return rc;
+    if ((long long)B * n == 0) return GAD_OK;
+    GAD_REQUIRE(workspace, GAD_ERR_NULL, "three_nn_grid: null pointer (workspace)");
+    GAD_REQUIRE((reinterpret_cast<size_t>(workspace) & 7) == 0, GAD_ERR_SHAPE, "three_nn_grid: the workspace must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (!g_opt_tnn_grid) {
+        const int tiles = gad_cdiv(n, 256);
+        hipLaunchKernelGGL(three_nn_kernel, dim3(B * tiles), dim3(256), 0, st, unknown, known, n, m, tiles, dist2, idx);
+        if (stats) hipLaunchKernelGGL(tnn_stats_exhaustive_kernel, dim3(1), dim3(64), 0, st, B, n, stats);
+        GAD_CHECK_LAUNCH("three_nn_grid(exhaustive)");
+        return GAD_OK;
+    }
+    char* w = static_cast<char*>(workspace);
+    float* part = reinterpret_cast<float*>(w);
+    BqgGrid* hdr = reinterpret_cast<BqgGrid*>(w + pl.o_hdr);
+    int32_t* cellof = reinterpret_cast<int32_t*>(w + pl.o_cellof);
+    int32_t* rank = reinterpret_cast<int32_t*>(w + pl.o_rank);
+    int32_t* table = reinterpret_cast<int32_t*>(w + pl.o_table);
+    int32_t* start = reinterpret_cast<int32_t*>(w + pl.o_start);
+    float4* sorted = reinterpret_cast<float4*>((reinterpret_cast<size_t>(w + pl.o_sorted) + 15) & ~(size_t)15);
+    const int pt_grid = (int)std::min<long long>(1024, gad_cdiv(m, 256));
+    // a wavefront takes a run of per_wave queries of one cloud: about TNN_WAVES_TARGET wavefronts, one query each below that
+    const int per_wave = (int)std::max<long long>(1, gad_cdiv((long long)B * n, TNN_WAVES_TARGET));
+    hipLaunchKernelGGL(bqg_bounds_kernel, dim3(pl.parts, B), dim3(256), 0, st, known, m, part, table,
+                       (long long)B * pl.slices * pl.cells);
+    hipLaunchKernelGGL(tnn_setup_kernel, dim3(B), dim3(64), 0, st, part, pl.parts, pl.cells, hdr, stats);
+    hipLaunchKernelGGL(bqg_count_kernel, dim3(B * pl.slices), dim3(64), 0, st, known, m, pl.slices, pl.slice, pl.cells, hdr, cellof, rank,
+                       table);
+    hipLaunchKernelGGL(bqg_slices_kernel, dim3(gad_cdiv(pl.cells, 256), B), dim3(256), 0, st, pl.slices, pl.cells, hdr, table, start);
+    hipLaunchKernelGGL(bqg_scan_kernel, dim3(B), dim3(1024), 0, st, m, pl.cells, hdr, start);
+    hipLaunchKernelGGL(bqg_scatter_kernel, dim3(pt_grid, B), dim3(256), 0, st, known, m, pl.slices, pl.slice, pl.cells, cellof, rank, table,
+                       start, sorted);
+    hipLaunchKernelGGL(tnn_query_kernel, dim3(gad_cdiv(gad_cdiv(n, per_wave), 4), B), dim3(256), 0, st, unknown, known, n, m, per_wave,
+                       pl.cells, hdr, start, sorted, dist2, idx, stats);
+    GAD_CHECK_LAUNCH("three_nn_grid");
     return GAD_OK;
 }
 

@@ -89,6 +89,7 @@ const std::vector<reg_entry>& registry() {
         GAD_PLAN_ENTRY(gad_group_points)
         GAD_PLAN_ENTRY(gad_group_points_grad)
         GAD_PLAN_ENTRY(gad_three_nn)
+        GAD_PLAN_ENTRY(gad_three_nn_grid)
         GAD_PLAN_ENTRY(gad_three_interpolate)
         GAD_PLAN_ENTRY(gad_three_interpolate_grad)
         GAD_PLAN_ENTRY(gad_query_and_group)

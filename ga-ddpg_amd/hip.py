@@ -151,7 +151,7 @@ EXPORTS = (
     "gad_fps_tiled_workspace_bytes", "gad_fps_tiled",
     "gad_gather_points_grad", "gad_ball_query", "gad_ball_query_grid_workspace_bytes", "gad_ball_query_grid",
     "gad_group_points", "gad_group_points_grad",
-    "gad_three_nn", "gad_three_interpolate", "gad_three_interpolate_grad",
+    "gad_three_nn", "gad_three_nn_grid_workspace_bytes", "gad_three_nn_grid", "gad_three_interpolate", "gad_three_interpolate_grad",
     "gad_query_and_group", "gad_prep_points", "gad_rows_from_ball_query", "gad_rows_group_all",
     "gad_gemm_fwd", "gad_bn_finalize", "gad_bn_eval_affine", "gad_segment_pool", "gad_pool_finalize", "gad_affine_act", "gad_transpose_batched",
     "gad_pool_bwd_stats", "gad_bn_bwd_coef", "gad_gemm_dx", "gad_gemm_dw", "gad_gemm_bwd", "gad_gemm_dw_reduce", "gad_critic_loss",
@@ -171,13 +171,16 @@ _SIGNATURES = {
     "gad_ball_query_grid_workspace_bytes": [C.c_int, C.c_int, C.c_int, C.c_int],
     "gad_ball_query_grid": [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, _vp, _vp, _vp],
     "gad_three_nn": [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp],
+    "gad_three_nn_grid_workspace_bytes": [C.c_int, C.c_int, C.c_int],
+    "gad_three_nn_grid": [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp],
     "gad_three_interpolate": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
     "gad_three_interpolate_grad": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
 }
 
 
 # every other entry point returns an int status
-_RESTYPES = {"gad_fps_tiled_workspace_bytes": C.c_longlong, "gad_ball_query_grid_workspace_bytes": C.c_longlong}
+_RESTYPES = {"gad_fps_tiled_workspace_bytes": C.c_longlong, "gad_ball_query_grid_workspace_bytes": C.c_longlong,
+             "gad_three_nn_grid_workspace_bytes": C.c_longlong}
 
 
 def workspace(name, device, *shape):
@@ -262,7 +265,7 @@ def require_cuda(*tensors):
 
 # options this package sets when it loads the library (the library's own default of "mfma_split" is 0 = the f32 MFMA: a plain C
 # caller opts in itself); also what a test restores
-OPTION_DEFAULTS = {"mfma_split": 1, "deterministic": 0}
+OPTION_DEFAULTS = {"mfma_split": 1, "deterministic": 0, "tnn_grid": 1}
 
 
 def get_option_default(name):

@@ -9,7 +9,8 @@ wrapper.  Modules hold ordinary nn.Parameters; the fused update step (core.agent
 flat buffers.
 
 PointnetFPModule (feature propagation, `mlp` = one shared MLP, keys `mlp.{0,1,3,4,...}.*`): three_nn and three_interpolate of
-libgaddpg, the shared MLP as torch modules."""
+libgaddpg, the shared MLP as torch modules; three_nn takes the grid search of gad_three_nn_grid for the cloud sizes of
+pointnet2_utils.three_nn_uses_grid and the exhaustive gad_three_nn otherwise -- same neighbours, so the same output."""
 import torch.nn as nn
 
 from . import pointnet2_utils
@@ -114,7 +115,9 @@ class PointnetFPModule(nn.Module):
     """feature propagation: the features of `known` (B,m,3) are carried to `unknown` (B,n,3) by inverse-distance weights over the
     three nearest known points (pointnet2_utils.three_nn / three_interpolate: libgaddpg section A kernels, differentiable in the
     features), concatenated with the skip features and passed through the shared MLP as torch modules -- the route
-    _generic_forward takes for the non-fused set-abstraction forms"""
+    _generic_forward takes for the non-fused set-abstraction forms.  The cost in m: three_nn searches a uniform grid over `known`
+    (gad_three_nn_grid) where pointnet2_utils.three_nn_uses_grid(n, m) holds and walks all m known points per query otherwise;
+    the indices, the distances and hence the output and every gradient are the same bit for bit on either route"""
 
     def __init__(self, mlp, bn=True):
         super().__init__()

@@ -9,7 +9,11 @@ LDS run gad_furthest_point_sampling, every other shape gad_fps_tiled -- same ind
 and more (ball_query_uses_grid: the sizes at which it was measured faster, profiles/ball_query_grid.txt) to gad_ball_query_grid, a
 uniform grid in global memory, and every other shape to gad_ball_query -- same indices; library option "bq_grid" = 0 keeps the scan
 for all of them, 2 sends every cloud beyond 4096 points to the grid.  The fused set-abstraction modules (sa_function, i.e.
-PointnetSAModule[MSG] with bn=True, use_xyz=True and features) route by the same two predicates.  What is left of the LDS
+PointnetSAModule[MSG] with bn=True, use_xyz=True and features) route by the same two predicates.  three_nn -- and with it
+PointnetFPModule -- sends clouds of 8192 known points and more (three_nn_uses_grid: the sizes at which the grid was measured
+faster, profiles/three_nn_grid.txt) to gad_three_nn_grid, which searches the same grid ring by ring instead of evaluating all n * m
+distances, and every other shape to gad_three_nn -- same distances and indices; library option "tnn_grid" = 0 keeps gad_three_nn
+for all of them, 2 sends every shape with more than 1024 known points to the grid.  What is left of the LDS
 kernels' refusals (N > 16384, npoint > N, 3N + npoint beyond 160 KiB of LDS) is engine.Geometry: the update step and
 feature_forward call gad_furthest_point_sampling directly."""
 import torch
@@ -43,6 +47,26 @@ def ball_query_uses_grid(N):
     if mode == 0 or N <= BQ_LDS_MAX_N:
         return False
     return mode >= 2 or N >= BQ_GRID_MIN_N
+
+
+TNN_LDS_TILE = 1024       # known points per LDS tile of gad_three_nn: a cloud of one tile is never sent to the grid
+# smallest known cloud sent to gad_three_nn_grid by default.  profiles/three_nn_grid.txt (MI355X; B = 1 and 8; n = m / 4, m, 4 m;
+# box-surface and uniform-cube clouds with queries of the same distribution, and cube clouds with 70 % of the queries outside the
+# box; us per call): building the grid costs about 190 us, gad_three_nn about 90 ns per known point -- at m = 2048 the two tie
+# (0.72-1.06), at m = 4096 the grid wins 17 of 18 rows (1.1-1.9 x) and loses one (0.92: B 8, n 16384, queries outside the box), from
+# m = 8192 it wins every measured row by far more than the spread of a row (< 3 %): 1.3-3.4 x at 8192, 2.2-6.5 x at 16384,
+# 1.9-22 x at 65536, 3.4-38 x at 262144 (n = m = 262144: 19.5 ms -> 0.8 ms).
+TNN_GRID_MIN_M = 8192
+
+
+def three_nn_uses_grid(n, m):
+    """the shapes three_nn (hence PointnetFPModule) sends to gad_three_nn_grid.  Library option "tnn_grid": 1 (default) = clouds of
+    TNN_GRID_MIN_M known points and more, whatever n; 0 = none; 2 = every shape with more known points than the TNN_LDS_TILE of
+    gad_three_nn's kernel"""
+    mode = hip.get_option("tnn_grid")
+    if mode == 0 or m <= TNN_LDS_TILE:
+        return False
+    return mode >= 2 or m >= TNN_GRID_MIN_M
 
 
 def furthest_point_sample(xyz, npoint):
@@ -129,7 +153,8 @@ def grouping_operation(features, idx):
 def three_nn(unknown, known):
     """unknown (B,n,3), known (B,m,3) float32 CUDA contiguous -> (dist (B,n,3) float32, idx (B,n,3) int32): the three nearest
     known points of every query point, nearest first, ties to the lower index; dist is the Euclidean distance (the square root of
-    what gad_three_nn returns).  Neither output is differentiable."""
+    what gad_three_nn returns).  Shapes for which three_nn_uses_grid holds go to gad_three_nn_grid (a uniform grid over the known
+    points, a workspace per call), every other shape to gad_three_nn: same outputs bit for bit.  Neither output is differentiable."""
     _check(unknown, known)
     if unknown.dtype != torch.float32 or known.dtype != torch.float32:
         raise RuntimeError("unknown and known must be float tensors")
@@ -137,6 +162,10 @@ def three_nn(unknown, known):
     m = known.shape[1]
     dist2 = torch.empty(B, n, 3, dtype=torch.float32, device=unknown.device)
     idx = torch.empty(B, n, 3, dtype=torch.int32, device=unknown.device)
+    if three_nn_uses_grid(n, m):
+        hip.call("gad_three_nn_grid", unknown.detach(), known.detach(), B, n, m, dist2, idx, None,
+                 hip.workspace("gad_three_nn_grid", unknown.device, B, n, m))
+        return torch.sqrt(dist2), idx
     hip.call("gad_three_nn", unknown.detach(), known.detach(), B, n, m, dist2, idx)
     return torch.sqrt(dist2), idx
 

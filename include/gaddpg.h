@@ -60,7 +60,9 @@ int gad_abi_version(void);                 /* bumped on any signature change or 
                                             * gad_fps_tiled_workspace_bytes (additive: furthest point sampling without
                                             * the size limits of gad_furthest_point_sampling); gad_ball_query_grid and
                                             * gad_ball_query_grid_workspace_bytes, option "bq_grid" (additive: the radius
-                                            * search through a uniform grid in global memory)                           */
+                                            * search through a uniform grid in global memory); gad_three_nn_grid and
+                                            * gad_three_nn_grid_workspace_bytes, option "tnn_grid" (additive: three_nn
+                                            * through the same grid)                                                    */
 /* diagnostics: which kernel family the last gad_gemm_fwd / _dx / _dw / _bwd call routed to ("gemm_fwd(stream)",
  * "gemm_dx(wide)", "gemm_bwd(stream)", "gemm_dw" = generic tile kernel, ...); bench.py labels its per-kernel table
  * with it instead of restating the routing rules.                                                  */
@@ -217,6 +219,43 @@ int gad_group_points_grad(const float* grad_out, const int32_t* idx, int B, int 
  * the square root is taken by the caller (pointnet2_utils.three_nn), as upstream does.  No limit on n or m beyond int32.
  * B * n == 0: GAD_OK without a launch; otherwise m < 1 is GAD_ERR_SHAPE, as is any negative size.                            */
 int gad_three_nn(const float* unknown, const float* known, int B, int n, int m, float* dist2, int32_t* idx, void* stream);
+/* gad_three_nn costs n * m distance evaluations per cloud (every query lane walks all m known points through LDS tiles).
+ *
+ * gad_three_nn_grid: the same operator, dist2 and idx equal to gad_three_nn's bit for bit for every input -- the three known points
+ * smallest under the total order (d, index), ascending, d evaluated as above for every candidate; a d that is NaN or +inf is never
+ * taken, unfilled slots hold (+inf, 0), distances are squared -- through a uniform grid per cloud over the KNOWN points in global
+ * memory: any n >= 0 and m >= 1.  Each cloud's finite known points give its bounding box; the cell edge is chosen on the device
+ * from that box and a budget of min(max(m / 4, 64), 65536) cells (at most 1024 per axis) that the host derives from m alone: an axis
+ * of zero extent gets one cell, a box whose extent overflows ends in one cell; gad_ball_query_grid's stable counting sort lists
+ * the known points by cell.  A wavefront per query tests the 3 x 3 x 3 cells around the query's cell (a query outside the box is
+ * clamped to a border cell), then the shells of cells around that block, and stops at the first ring after which every
+ * unexamined point is provably farther than the current third-best d, strictly (a point at equal d and lower index would win):
+ * the bound is the distance to the nearest face of the examined block that is not a border of the grid -- combined, for a query
+ * outside the box, with its distance to the box along the other axes -- less the rounding of the cell function and of d
+ * (derived in csrc/geometry.hip), so the test may search one ring too many, never one too few; the search
+ * also ends when the block covers the grid (fewer than three finite points, m < 3).  A query with a non-finite coordinate
+ * returns (+inf, 0) x 3 without a search.  A query unresolved after 3 rings (far outside the box, in a large void) is redone
+ * by an exhaustive walk of its cloud in the same launch: exact, only slower.
+ * stats (nullable, (B,2) i32): [b][0] = queries of cloud b answered from the grid (those with a non-finite coordinate included),
+ * [b][1] = queries redone exhaustively; [b][0] + [b][1] = n.  The call writes them -- the caller does not clear them -- with
+ * integer adds, at most one per counter and wavefront, and only when the pointer is given.
+ * The call enqueues seven launches on `stream` (bounds, grid set-up, per-slice stable ranks, slice prefix, cell prefix, scatter,
+ * query) ordered by the stream alone -- no workgroup waits for another inside a launch, no host synchronisation, no allocation;
+ * every loop is bounded by the grid's dimensions or by m.  There is no float atomic: the outputs do not depend on scheduling and
+ * option "deterministic" changes nothing here.  Workspace contract as for gad_fps_tiled: caller-allocated DEVICE memory of at
+ * least gad_three_nn_grid_workspace_bytes(B, n, m) bytes, 8-byte aligned, uninitialised on entry, owned by the call until its
+ * launches have run on `stream`, free to reuse afterwards (also for another shape it is large enough for).  It holds, per cloud,
+ * the bounding-box partials, the grid header, cell (m) i32, rank (m) i32, the per-slice cell counts, the cell starts and the
+ * sorted (x, y, z, index) (m) x 16 bytes: the size depends on B and m only, is >= B * m * 24 and grows with m.
+ * B * n == 0: GAD_OK without a launch (workspace may then be NULL).  Otherwise GAD_ERR_NULL / GAD_ERR_SHAPE: null pointers, m < 1,
+ * a negative size, 3 * m, B * m or B * n beyond 2^31, B beyond 65535, a misaligned workspace;
+ * gad_three_nn_grid_workspace_bytes applies the same shape checks and returns the negative gad_status.
+ * Option "tnn_grid" [1]: 0 = the entry point runs gad_three_nn's kernel (stats then read [0, n]) and pointnet2_utils.three_nn
+ * calls gad_three_nn; 1 = the Python route follows the measured rule (profiles/three_nn_grid.txt); 2 = it sends every shape with
+ * m > 1024 (one LDS tile of gad_three_nn) to the grid.  Same results whatever the value.                                      */
+long long gad_three_nn_grid_workspace_bytes(int B, int n, int m);
+int gad_three_nn_grid(const float* unknown, const float* known, int B, int n, int m, float* dist2, int32_t* idx,
+                      int32_t* stats /*nullable, (B,2)*/, void* workspace, void* stream);
 
 /* three_interpolate(points (B,C,m), idx (B,n,3), weight (B,n,3)) -> out (B,C,n):
  *   out[b,c,i] = (w0 * f[idx0] + w1 * f[idx1]) + w2 * f[idx2],   f = points[b,c,:]
