@@ -7,6 +7,7 @@
 // shuffle arg-max for FPS (one workgroup per cloud, no global scratch), 16-byte coalesced
 // streams for the materialising group kernels.
 #include "common.hpp"
+#include "point_grid.hpp"
 #include <algorithm>
 #include <type_traits>
 
@@ -1160,19 +1161,7 @@ extern "C" int gad_ball_query(const float* new_xyz, const float* xyz, int B, int
 // ball holds fewer than nsample of them -- the usual first-stage case.  Here every cloud is sorted once into a uniform grid
 // (cell edge >= 1.002 x radius: every in-radius point lies in the 3x3x3 cells around the centroid's cell) and a wavefront
 // tests only those cells' points.  Seven launches on the caller's stream, no host synchronisation, nothing sized by the data:
-//   bounds   per-workgroup min / max over the points whose three coordinates are finite; clears the slice table
-//   setup    one wavefront per cloud: the box, then the finest grid of edge >= 1.002 r with <= BQG_GMAX cells per axis and
-//            <= `cells` in all (the budget the host derives from N alone); coarsened by 1.25 x per try until it fits
-//   count    STABLE ranks.  A cloud is cut into `slices` contiguous index ranges, one wavefront each, which walks its range in
-//            index order 64 points at a time: the lanes of one cell are ranked by lane, and the slice's running count of that
-//            cell -- a row of the table that belongs to this wavefront alone -- is advanced by the cell's lowest lane.  The
-//            add is an integer atomic only so that the next 64 points read it coherently: no other wavefront touches the row
-//            and the adds of one wavefront are issued one after another (each result is consumed before the next is issued),
-//            so the value returned is the count over the slice's EARLIER points, whatever the rest of the chip does.
-//   slices   per cell: exclusive prefix of the slices' counts in slice order (in place), total -> start[cell]
-//   scan     one workgroup per cloud: exclusive prefix over the cells
-//   scatter  sorted[start[cell] + prefix[slice][cell] + rank] = (x, y, z, index): a stable counting sort, indices ascending
-//            inside every cell and the same array whatever the scheduling
+// the six of point_grid_build (point_grid.hip: bounds, setup with the edge taken from the radius, count, slices, scan, scatter), then
 //   query    one wavefront per centroid: the nine (y, z) rows of three x-adjacent cells are nine contiguous runs of `sorted`;
 //            every candidate gets the exact pinned-order predicate of the scan, hits are collected in LDS, and the nsample
 //            smallest are placed by rank (number of smaller hit indices) -- the scan's ascending order whatever cell a
@@ -1180,196 +1169,11 @@ extern "C" int gad_ball_query(const float* new_xyz, const float* xyz, int B, int
 //            and cheap in that regime because it stops at nsample hits.
 // The grid only selects candidates.  Its cell function is monotone in the coordinate and clamped, so a centroid outside the box
 // lands in a border cell that still has every candidate next to it; a non-finite coordinate maps to a valid cell and fails the
-// predicate.  Rounding: (p - lo) * inv is off by < 1.3e-4 cells at BQG_GMAX cells per axis, the edge has 2e-3 of slack.
-#define BQG_GMAX 1024                              // cells per axis
-#define BQG_MAXCELLS 65536                         // cells per cloud
-#define BQG_MAXSLICES 64                           // index ranges per cloud (count pass)
-#define BQG_MAXPARTS 64                            // bounding-box partials per cloud
+// predicate.  Rounding: (p - lo) * inv is off by < 1.3e-4 cells at PG_GMAX cells per axis, the edge has 2e-3 of slack.
 #define BQG_HITS 512                               // hits of one centroid held in LDS
 
-struct BqgGrid { float lox, loy, loz, ivx, ivy, ivz; int32_t nx, ny, nz, ncells; int32_t reserved_[6]; };   // 64 bytes
-
-__device__ __forceinline__ bool bqg_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-// monotone in p, in [0, n) for every p (NaN -> 0)
-__device__ __forceinline__ int bqg_cell1(float p, float lo, float inv, int n) {
-    const float f = (p - lo) * inv;
-    return f >= (float)(n - 1) ? n - 1 : (f > 0.f ? (int)f : 0);
-}
-__device__ __forceinline__ void bqg_wave_sync() {                 // LDS written by some lanes of a wavefront, read by others
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ void bqg_wave_minmax(float (&lo)[3], float (&hi)[3]) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64));
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64));
-        }
-}
-
-__global__ __launch_bounds__(256) void bqg_bounds_kernel(const float* __restrict__ xyz, int N, float* __restrict__ part,
-                                                         int32_t* __restrict__ table, long long table_ints) {
-    __shared__ float red[4][6];
-    const int b = blockIdx.y, tid = threadIdx.x, parts = gridDim.x;
-    const float* p = xyz + (size_t)b * N * 3;
-    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-    for (int k = blockIdx.x * 256 + tid; k < N; k += parts * 256) {
-        const float v[3] = {p[k * 3 + 0], p[k * 3 + 1], p[k * 3 + 2]};
-        if (bqg_finite(v[0]) && bqg_finite(v[1]) && bqg_finite(v[2])) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], v[a]); hi[a] = fmaxf(hi[a], v[a]); }
-        }
-    }
-    bqg_wave_minmax(lo, hi);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { red[tid >> 6][a] = lo[a]; red[tid >> 6][3 + a] = hi[a]; }
-    }
-    __syncthreads();
-    if (tid < 6) {
-        float v = red[0][tid];
-        for (int w = 1; w < 4; ++w) v = tid < 3 ? fminf(v, red[w][tid]) : fmaxf(v, red[w][tid]);
-        part[((size_t)b * parts + blockIdx.x) * 6 + tid] = v;
-    }
-    const long long me = (long long)blockIdx.y * parts + blockIdx.x, stride = (long long)gridDim.y * parts * 256;
-    for (long long i = me * 256 + tid; i < table_ints; i += stride) table[i] = 0;
-}
-
-__device__ __forceinline__ int bqg_axis(float ext, float inv) {   // cells of edge 1 / inv along an extent; NaN / huge -> over the cap
-    const float f = ext * inv;
-    return f < (float)(2 * BQG_GMAX) ? (int)f + 1 : 2 * BQG_GMAX + 1;
-}
-
-__global__ __launch_bounds__(64) void bqg_setup_kernel(const float* __restrict__ part, int parts, float radius, int cells,
-                                                       BqgGrid* __restrict__ hdr) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-    if (lane < parts) {
-        const float* q = part + ((size_t)b * parts + lane) * 6;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { lo[a] = q[a]; hi[a] = q[3 + a]; }
-    }
-    bqg_wave_minmax(lo, hi);
-    if (lane != 0) return;
-    if (!(hi[0] >= lo[0])) {                                      // a cloud without a finite point: one cell at the origin
-#pragma unroll
-        for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0.f;
-    }
-    const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];           // >= 0; +inf where the box overflows
-    float h = radius * 1.002f, inv = 0.f;
-    int nx = 1, ny = 1, nz = 1;
-    bool fits = false;
-    for (int it = 0; it < 512 && !fits; ++it) {                   // 1.25^512 covers the whole float range
-        inv = 1.0f / h;
-        nx = bqg_axis(ex, inv); ny = bqg_axis(ey, inv); nz = bqg_axis(ez, inv);
-        fits = nx <= BQG_GMAX && ny <= BQG_GMAX && nz <= BQG_GMAX && (long long)nx * ny * nz <= (long long)cells;
-        h *= 1.25f;
-    }
-    if (!fits) { nx = ny = nz = 1; inv = 0.f; }                  // (an infinite extent: every point in the one cell)
-    BqgGrid g;
-    g.lox = lo[0]; g.loy = lo[1]; g.loz = lo[2];
-    g.ivx = g.ivy = g.ivz = inv;
-    g.nx = nx; g.ny = ny; g.nz = nz; g.ncells = nx * ny * nz;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) g.reserved_[a] = 0;
-    hdr[b] = g;
-}
-
-__global__ __launch_bounds__(64) void bqg_count_kernel(const float* __restrict__ xyz, int N, int slices, int slice, int cells,
-                                                       const BqgGrid* __restrict__ hdr, int32_t* __restrict__ cellof,
-                                                       int32_t* __restrict__ rank, int32_t* __restrict__ table) {
-    const int b = blockIdx.x / slices, q = blockIdx.x - b * slices, lane = threadIdx.x;
-    const BqgGrid g = hdr[b];
-    const float* p = xyz + (size_t)b * N * 3;
-    int32_t* row = table + ((size_t)b * slices + q) * cells;
-    int32_t* co = cellof + (size_t)b * N;
-    int32_t* rk = rank + (size_t)b * N;
-    const int k0 = q * slice, k1 = min(N, k0 + slice);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (int base = k0; base < k1; base += 64) {
-        const int k = base + lane;
-        const bool live = k < k1;
-        int cell = -1;
-        if (live)
-            cell = (bqg_cell1(p[k * 3 + 2], g.loz, g.ivz, g.nz) * g.ny + bqg_cell1(p[k * 3 + 1], g.loy, g.ivy, g.ny)) * g.nx +
-                   bqg_cell1(p[k * 3 + 0], g.lox, g.ivx, g.nx);
-        // the lanes of one cell: rank by lane, the lowest lane leads
-        int before = 0, total = 0, leader = lane;
-        unsigned long long todo = __ballot(live);
-        while (todo) {                                            // wave-uniform
-            const int l0 = __ffsll((long long)todo) - 1;
-            const int c0 = __shfl(cell, l0, 64);
-            const unsigned long long m = __ballot(live && cell == c0);
-            if (live && cell == c0) { before = __popcll(m & below); total = __popcll(m); leader = l0; }
-            todo &= ~m;
-        }
-        int seen = 0;                                             // points of this cell earlier in the slice
-        if (live && leader == lane) seen = __hip_atomic_fetch_add(row + cell, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        seen = __shfl(seen, leader, 64);                          // (consumes the result: the next group's adds follow it)
-        if (live) { co[k] = cell; rk[k] = seen + before; }
-    }
-}
-
-__global__ __launch_bounds__(256) void bqg_slices_kernel(int slices, int cells, const BqgGrid* __restrict__ hdr,
-                                                         int32_t* __restrict__ table, int32_t* __restrict__ start) {
-    const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= hdr[b].ncells) return;
-    int32_t* t = table + (size_t)b * slices * cells + c;
-    int run = 0;
-    for (int q = 0; q < slices; ++q) {
-        const int v = t[(size_t)q * cells];
-        t[(size_t)q * cells] = run;
-        run += v;
-    }
-    start[(size_t)b * (cells + 1) + c] = run;
-}
-
-__global__ __launch_bounds__(1024) void bqg_scan_kernel(int N, int cells, const BqgGrid* __restrict__ hdr,
-                                                        int32_t* __restrict__ start) {
-    __shared__ int sums[1024];
-    const int b = blockIdx.x, tid = threadIdx.x, n = hdr[b].ncells;
-    int32_t* s = start + (size_t)b * (cells + 1);
-    const int per = (n + 1023) / 1024, c0 = min(n, tid * per), c1 = min(n, c0 + per);
-    int sum = 0;
-    for (int c = c0; c < c1; ++c) sum += s[c];
-    sums[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int v = tid >= o ? sums[tid - o] : 0;
-        __syncthreads();
-        sums[tid] += v;
-        __syncthreads();
-    }
-    int run = sums[tid] - sum;
-    for (int c = c0; c < c1; ++c) {
-        const int v = s[c];
-        s[c] = run;
-        run += v;
-    }
-    if (tid == 0) s[n] = N;
-}
-
-__global__ __launch_bounds__(256) void bqg_scatter_kernel(const float* __restrict__ xyz, int N, int slices, int slice, int cells,
-                                                          const int32_t* __restrict__ cellof, const int32_t* __restrict__ rank,
-                                                          const int32_t* __restrict__ table, const int32_t* __restrict__ start,
-                                                          float4* __restrict__ sorted) {
-    const int b = blockIdx.y;
-    const float* p = xyz + (size_t)b * N * 3;
-    const int32_t* t = table + (size_t)b * slices * cells;
-    const int32_t* s = start + (size_t)b * (cells + 1);
-    for (int k = blockIdx.x * 256 + threadIdx.x; k < N; k += gridDim.x * 256) {
-        const int cell = cellof[(size_t)b * N + k];
-        const int pos = s[cell] + t[(size_t)(k / slice) * cells + cell] + rank[(size_t)b * N + k];
-        if ((unsigned)pos < (unsigned)N)                           // (always: the three terms count disjoint sets of earlier points)
-            sorted[(size_t)b * N + pos] = make_float4(p[k * 3 + 0], p[k * 3 + 1], p[k * 3 + 2], __int_as_float(k));
-    }
-}
-
 __global__ __launch_bounds__(256) void bqg_query_kernel(const float* __restrict__ new_xyz, const float* __restrict__ xyz, int G, int N,
-                                                        int M, float r2, int nsample, int cells, const BqgGrid* __restrict__ hdr,
+                                                        int M, float r2, int nsample, int cells, const PointGrid* __restrict__ hdr,
                                                         const int32_t* __restrict__ start, const float4* __restrict__ sorted,
                                                         int32_t* __restrict__ idx, int32_t* __restrict__ cnt_out) {
     __shared__ int32_t hits[4][BQG_HITS];
@@ -1379,12 +1183,12 @@ __global__ __launch_bounds__(256) void bqg_query_kernel(const float* __restrict_
     const int b = gi / M;
     const float* c = new_xyz + (size_t)gi * 3;
     const float cx = c[0], cy = c[1], cz = c[2];
-    const BqgGrid g = hdr[b];
+    const PointGrid g = hdr[b];
     const int32_t* st = start + (size_t)b * (cells + 1);
     const float4* sp = sorted + (size_t)b * N;
     int32_t* out = idx + (size_t)gi * nsample;
     int32_t* my = hits[wave];
-    const int ix = bqg_cell1(cx, g.lox, g.ivx, g.nx), iy = bqg_cell1(cy, g.loy, g.ivy, g.ny), iz = bqg_cell1(cz, g.loz, g.ivz, g.nz);
+    const int ix = pg_cell1(cx, g.lox, g.ivx, g.nx), iy = pg_cell1(cy, g.loy, g.ivy, g.ny), iz = pg_cell1(cz, g.loz, g.ivz, g.nz);
     // lanes 0..8 take one (y, z) row each: its three x-adjacent cells are one run [rs, rs + rl) of the sorted cloud
     int rs = 0, rl = 0;
     if (lane < 9) {
@@ -1433,7 +1237,7 @@ __global__ __launch_bounds__(256) void bqg_query_kernel(const float* __restrict_
     if (H > BQG_HITS) {
         n = wave_ball_query(xyz + (size_t)b * N * 3, N, cx, cy, cz, r2, nsample, lane, out);
     } else {
-        bqg_wave_sync();
+        pg_wave_sync();
         int first = 0x7fffffff;
         for (int i = lane; i < H; i += 64) {
             const int mine = my[i];
@@ -1451,33 +1255,19 @@ __global__ __launch_bounds__(256) void bqg_query_kernel(const float* __restrict_
     if (lane == 0 && cnt_out) cnt_out[gi] = n;
 }
 
-// shapes, launch geometry and workspace layout (byte offsets, each a multiple of 256) of one call
-struct BqgPlan { int parts, slices, slice, cells; long long o_hdr, o_cellof, o_rank, o_table, o_start, o_sorted, total; };
-static long long bqg_up(long long v) { return (v + 255) & ~255ll; }
-static int bqg_plan(const char* who, int B, int N, int M, int nsample, BqgPlan* pl) {
+// the operator's shape check, the grid's checks and layout for a cloud of N points, the operator's launch bound: the parent's order
+static int bqg_plan(const char* who, int B, int N, int M, int nsample, PointGridPlan* pl) {
     GAD_REQUIRE(B >= 0 && N >= 1 && M >= 0 && nsample >= 1, GAD_ERR_SHAPE, "%s: unsupported shape B=%d N=%d M=%d nsample=%d", who, B, N,
                 M, nsample);
-    GAD_REQUIRE((long long)N * 3 < (1ll << 31) && (long long)B * N < (1ll << 31), GAD_ERR_SHAPE,
-                "%s: B * N = %d * %d points (or 3 * N) overflows 32-bit indexing", who, B, N);
+    const int rc = point_grid_plan(who, B, N, pl);
+    if (rc != GAD_OK) return rc;
     // (hipLaunchKernelGGL takes the grid in threads: B * M / 4 workgroups x 256 has to stay below 2^32)
     GAD_REQUIRE((long long)B * M < (1ll << 26) && B <= 65535, GAD_ERR_SHAPE, "%s: a grid of B * M = %d * %d centroids overflows", who, B, M);
-    pl->parts = (int)std::min<long long>(BQG_MAXPARTS, gad_cdiv(N, 4096));
-    pl->slices = (int)std::min<long long>(BQG_MAXSLICES, gad_cdiv(N, 2048));
-    pl->slice = gad_cdiv(gad_cdiv(N, pl->slices), 64) * 64;
-    pl->cells = std::max(64, std::min(BQG_MAXCELLS, N / 4));
-    long long o = bqg_up((long long)B * pl->parts * 6 * 4);                             // bounding-box partials at offset 0
-    pl->o_hdr = o;    o += bqg_up((long long)B * (long long)sizeof(BqgGrid));
-    pl->o_cellof = o; o += bqg_up((long long)B * N * 4);
-    pl->o_rank = o;   o += bqg_up((long long)B * N * 4);
-    pl->o_table = o;  o += bqg_up((long long)B * pl->slices * pl->cells * 4);
-    pl->o_start = o;  o += bqg_up((long long)B * (pl->cells + 1) * 4);
-    pl->o_sorted = o; o += bqg_up((long long)B * N * 16 + 16);                          // (+16: the float4 array is aligned inside)
-    pl->total = o;
     return GAD_OK;
 }
 
 extern "C" long long gad_ball_query_grid_workspace_bytes(int B, int N, int M, int nsample) {
-    BqgPlan pl;
+    PointGridPlan pl;
     const int rc = bqg_plan("ball_query_grid_workspace_bytes", B, N, M, nsample, &pl);
     return rc != GAD_OK ? rc : pl.total;
 }
@@ -1485,13 +1275,14 @@ extern "C" long long gad_ball_query_grid_workspace_bytes(int B, int N, int M, in
 extern "C" int gad_ball_query_grid(const float* new_xyz, const float* xyz, int B, int N, int M, float radius, int nsample,
                                    int32_t* idx, int32_t* cnt, void* workspace, void* stream) {
     GAD_REQUIRE(new_xyz && xyz && idx, GAD_ERR_NULL, "ball_query_grid: null pointer (new_xyz / xyz / idx)");
-    BqgPlan pl;
-    const int rc = bqg_plan("ball_query_grid", B, N, M, nsample, &pl);
+    PointGridPlan pl;
+    int rc = bqg_plan("ball_query_grid", B, N, M, nsample, &pl);
     if (rc != GAD_OK) return rc;
     const int G = B * M;
     if (G == 0) return GAD_OK;
-    GAD_REQUIRE(workspace, GAD_ERR_NULL, "ball_query_grid: null pointer (workspace)");
-    GAD_REQUIRE((reinterpret_cast<size_t>(workspace) & 7) == 0, GAD_ERR_SHAPE, "ball_query_grid: the workspace must be 8-byte aligned");
+    PointGridView v;
+    rc = point_grid_carve("ball_query_grid", workspace, pl, &v);
+    if (rc != GAD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const float r2 = radius * radius;
     if (!g_opt_bq_grid || !(radius > 0.f && radius < 1.0e18f)) {  // no grid for such a radius: the scan is right for every one
@@ -1499,26 +1290,9 @@ extern "C" int gad_ball_query_grid(const float* new_xyz, const float* xyz, int B
         GAD_CHECK_LAUNCH("ball_query_grid(scan)");
         return GAD_OK;
     }
-    char* w = static_cast<char*>(workspace);
-    float* part = reinterpret_cast<float*>(w);
-    BqgGrid* hdr = reinterpret_cast<BqgGrid*>(w + pl.o_hdr);
-    int32_t* cellof = reinterpret_cast<int32_t*>(w + pl.o_cellof);
-    int32_t* rank = reinterpret_cast<int32_t*>(w + pl.o_rank);
-    int32_t* table = reinterpret_cast<int32_t*>(w + pl.o_table);
-    int32_t* start = reinterpret_cast<int32_t*>(w + pl.o_start);
-    float4* sorted = reinterpret_cast<float4*>((reinterpret_cast<size_t>(w + pl.o_sorted) + 15) & ~(size_t)15);
-    const int pt_grid = (int)std::min<long long>(1024, gad_cdiv(N, 256));
-    hipLaunchKernelGGL(bqg_bounds_kernel, dim3(pl.parts, B), dim3(256), 0, st, xyz, N, part, table,
-                       (long long)B * pl.slices * pl.cells);
-    hipLaunchKernelGGL(bqg_setup_kernel, dim3(B), dim3(64), 0, st, part, pl.parts, radius, pl.cells, hdr);
-    hipLaunchKernelGGL(bqg_count_kernel, dim3(B * pl.slices), dim3(64), 0, st, xyz, N, pl.slices, pl.slice, pl.cells, hdr, cellof, rank,
-                       table);
-    hipLaunchKernelGGL(bqg_slices_kernel, dim3(gad_cdiv(pl.cells, 256), B), dim3(256), 0, st, pl.slices, pl.cells, hdr, table, start);
-    hipLaunchKernelGGL(bqg_scan_kernel, dim3(B), dim3(1024), 0, st, N, pl.cells, hdr, start);
-    hipLaunchKernelGGL(bqg_scatter_kernel, dim3(pt_grid, B), dim3(256), 0, st, xyz, N, pl.slices, pl.slice, pl.cells, cellof, rank, table,
-                       start, sorted);
-    hipLaunchKernelGGL(bqg_query_kernel, dim3(gad_cdiv(G, 4)), dim3(256), 0, st, new_xyz, xyz, G, N, M, r2, nsample, pl.cells, hdr, start,
-                       sorted, idx, cnt);
+    point_grid_build(xyz, B, N, pl, v, PG_EDGE_RADIUS, radius, nullptr, st);
+    hipLaunchKernelGGL(bqg_query_kernel, dim3(gad_cdiv(G, 4)), dim3(256), 0, st, new_xyz, xyz, G, N, M, r2, nsample, pl.cells, v.hdr,
+                       v.start, v.sorted, idx, cnt);
     GAD_CHECK_LAUNCH("ball_query_grid");
     return GAD_OK;
 }
@@ -1714,18 +1488,13 @@ extern "C" int gad_three_nn(const float* unknown, const float* known, int B, int
 }
 
 // ------------------------------------------------------------------------------------------------
-// three_nn of large clouds: the uniform grid of gad_ball_query_grid over the KNOWN points, searched ring by ring
+// three_nn of large clouds: the uniform grid of point_grid.hpp over the KNOWN points, searched ring by ring
 // ------------------------------------------------------------------------------------------------
-// three_nn_kernel evaluates all n * m distances.  Here each cloud's known points are sorted once into a uniform grid -- the
-// bounds / count / slices / scan / scatter launches of gad_ball_query_grid, unchanged -- and a wavefront per query tests the
-// 3 x 3 x 3 cells around the query's (clamped) cell, then the shells of cells around that block, until no unexamined point can
-// enter the answer.  Seven launches on the caller's stream, no host synchronisation, nothing sized by the data.
-//   setup    there is no radius: one wavefront per cloud picks the cell edge from the box of the finite points and the cell
-//            budget the host derives from m alone (min(max(m / 4, 64), 65536), the ball query's rule: about four points per
-//            cell of a cloud that fills its box).  The first edge is the one at which box volume / edge^3 (area / edge^2 and
-//            length / edge where one or two extents are zero) equals the budget, at least extent / BQG_GMAX; it is coarsened by
-//            1.1 x per try until the cells, counted as the cell function counts them, fit.  An axis of zero extent gets one
-//            cell, a box whose extent overflows ends in one cell (every point a candidate of the first block: still exact).
+// three_nn_kernel evaluates all n * m distances.  Here each cloud's known points are sorted once into a uniform grid -- the six
+// launches of point_grid_build, the cell edge picked from the box and the cell budget (there is no radius: point_grid.hip) --
+// and a wavefront per query tests the 3 x 3 x 3 cells around the query's (clamped) cell, then the shells of cells around that
+// block, until no unexamined point can enter the answer.  Seven launches on the caller's stream, no host synchronisation,
+// nothing sized by the data.
 //   query    a candidate is the 64-bit key (bits of d) << 32 | index: d = gad_sqdist >= +0 in the pinned order, so unsigned
 //            order of the keys IS the total order (d, index), and every key of a d that is +inf or NaN is >= the empty slot's
 //            key (+inf, 0) and fails the strict < of the insertion.  Each lane keeps the three smallest keys of the candidates
@@ -1740,7 +1509,7 @@ extern "C" int gad_three_nn(const float* unknown, const float* known, int B, int
 // a query, clamped to a border cell, would never see a bound as large as its distance to the box and would always fall back).
 // A point beyond a face is therefore at least sqrt(face^2 + out'^2 + out''^2) cells away, and the bound is the least of that
 // over the non-border faces.  Rounding: f is clamped to [-2048, 3072] first -- towards the box: every term only shrinks -- so
-// the computed (p - lo) * inv (two roundings, 1.2e-7 relative) is off by < 3.7e-4 cells for the query and, at <= BQG_GMAX
+// the computed (p - lo) * inv (two roundings, 1.2e-7 relative) is off by < 3.7e-4 cells for the query and, at <= PG_GMAX
 // cells per axis, < 1.3e-4 for a point (the same holds for the extent, whose computed cell count is < n), and a difference
 // of f and an integer by < 1.9e-4 more (one rounding at <= 3072): 6.9e-4 cells in all, TNN_CELL_SLACK = 1e-3 is taken off every
 // term.  With c2 the resulting sum of squares the point is at least L = sqrt(c2) / inv away, and its d, five roundings of
@@ -1814,61 +1583,6 @@ __device__ __forceinline__ void tnn_scan_runs(const float4* __restrict__ sp, int
     }
 }
 
-__global__ __launch_bounds__(64) void tnn_setup_kernel(const float* __restrict__ part, int parts, int cells,
-                                                       BqgGrid* __restrict__ hdr, int32_t* __restrict__ stats) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-    if (lane < parts) {
-        const float* q = part + ((size_t)b * parts + lane) * 6;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { lo[a] = q[a]; hi[a] = q[3 + a]; }
-    }
-    bqg_wave_minmax(lo, hi);
-    if (lane != 0) return;
-    if (stats) { stats[b * 2] = 0; stats[b * 2 + 1] = 0; }
-    if (!(hi[0] >= lo[0])) {                                      // a cloud without a finite point: one cell at the origin
-#pragma unroll
-        for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0.f;
-    }
-    const float e[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};                 // >= 0; +inf where the box overflows
-    // the edge at which the box, over the axes it extends along, is cut into `cells` cells (roots first: no overflow)
-    float h = 1.f, emax = 0.f;
-    int dims = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        if (e[a] > 0.f) { ++dims; emax = fmaxf(emax, e[a]); }
-    }
-    if (dims == 3) {
-        h = cbrtf(e[0]) * cbrtf(e[1]) * cbrtf(e[2]) / cbrtf((float)cells);
-    } else if (dims == 2) {
-        h = 1.f;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) h *= e[a] > 0.f ? sqrtf(e[a]) : 1.f;
-        h /= sqrtf((float)cells);
-    } else if (dims == 1) {
-        h = emax / (float)cells;
-    }
-    h = fmaxf(h, emax * (1.0f / (float)BQG_GMAX));
-    if (!(h > 1.0e-30f)) h = 1.0e-30f;                            // (1 / h stays finite)
-    float inv = 0.f;
-    int nx = 1, ny = 1, nz = 1;
-    bool fits = false;
-    for (int it = 0; it < 256 && !fits; ++it) {                   // (the first edge is within 1024 x of one that fits)
-        inv = 1.0f / h;
-        nx = bqg_axis(e[0], inv); ny = bqg_axis(e[1], inv); nz = bqg_axis(e[2], inv);
-        fits = nx <= BQG_GMAX && ny <= BQG_GMAX && nz <= BQG_GMAX && (long long)nx * ny * nz <= (long long)cells;
-        h *= 1.1f;
-    }
-    if (!fits) { nx = ny = nz = 1; inv = 0.f; }                  // (an infinite extent: every point in the one cell)
-    BqgGrid g;
-    g.lox = lo[0]; g.loy = lo[1]; g.loz = lo[2];
-    g.ivx = g.ivy = g.ivz = inv;
-    g.nx = nx; g.ny = ny; g.nz = nz; g.ncells = nx * ny * nz;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) g.reserved_[a] = 0;
-    hdr[b] = g;
-}
-
 // one axis of the stop test, in cells: `face` = the query's distance to the nearest face of the block [i - r, i + r] that is not
 // a border of the grid (+inf: none), `out` = its distance to the box (0 inside); f is the query's computed cell coordinate
 __device__ __forceinline__ void tnn_axis(float f, int i, int r, int n, float& face, float& out) {
@@ -1884,7 +1598,7 @@ __device__ __forceinline__ float tnn_sq_less_slack(float cells) {
 }
 
 __global__ __launch_bounds__(256) void tnn_query_kernel(const float* __restrict__ unknown, const float* __restrict__ known, int n,
-                                                        int m, int per_wave, int cells, const BqgGrid* __restrict__ hdr,
+                                                        int m, int per_wave, int cells, const PointGrid* __restrict__ hdr,
                                                         const int32_t* __restrict__ start, const float4* __restrict__ sorted,
                                                         float* __restrict__ dist2, int32_t* __restrict__ idx,
                                                         int32_t* __restrict__ stats) {
@@ -1892,7 +1606,7 @@ __global__ __launch_bounds__(256) void tnn_query_kernel(const float* __restrict_
     const long long q0 = ((long long)blockIdx.x * 4 + wave) * per_wave;
     if (q0 >= n) return;                                          // wave-uniform; the kernel has no workgroup barrier
     const int q1 = (int)min((long long)n, q0 + per_wave);
-    const BqgGrid g = hdr[b];
+    const PointGrid g = hdr[b];
     const int32_t* st = start + (size_t)b * (cells + 1);
     const float4* sp = sorted + (size_t)b * m;
     const float* kb = known + (size_t)b * m * 3;
@@ -1902,10 +1616,10 @@ __global__ __launch_bounds__(256) void tnn_query_kernel(const float* __restrict_
         const size_t o3 = ((size_t)b * n + i) * 3;
         const float ux = unknown[o3], uy = unknown[o3 + 1], uz = unknown[o3 + 2];
         tnn_key k0 = TNN_INF_KEY, k1 = TNN_INF_KEY, k2 = TNN_INF_KEY, g0 = TNN_INF_KEY, g1 = TNN_INF_KEY, g2 = TNN_INF_KEY;
-        bool done = !(bqg_finite(ux) && bqg_finite(uy) && bqg_finite(uz));
+        bool done = !(pg_finite(ux) && pg_finite(uy) && pg_finite(uz));
         if (!done) {
             const float fx = (ux - g.lox) * g.ivx, fy = (uy - g.loy) * g.ivy, fz = (uz - g.loz) * g.ivz;
-            const int ix = bqg_cell1(ux, g.lox, g.ivx, g.nx), iy = bqg_cell1(uy, g.loy, g.ivy, g.ny), iz = bqg_cell1(uz, g.loz, g.ivz, g.nz);
+            const int ix = pg_cell1(ux, g.lox, g.ivx, g.nx), iy = pg_cell1(uy, g.loy, g.ivy, g.ny), iz = pg_cell1(uz, g.loz, g.ivz, g.nz);
             for (int r = 1; r <= TNN_RINGS && !done; ++r) {
                 // lane = one (y, z) row of the (2r + 1)^2 around the query's: on the shell's y / z faces (and in the first block)
                 // the whole x run of the block, else its two end cells, one per pass
@@ -1973,17 +1687,17 @@ __global__ __launch_bounds__(64) void tnn_stats_exhaustive_kernel(int B, int n, 
     for (int b = threadIdx.x; b < B; b += 64) { stats[b * 2] = 0; stats[b * 2 + 1] = n; }
 }
 
-// the shape checks of gad_three_nn_grid; the workspace is gad_ball_query_grid's for a cloud of max(m, 1) points
-static int tnn_plan(const char* who, int B, int n, int m, BqgPlan* pl) {
+// the shape checks of gad_three_nn_grid, then the grid's for a cloud of max(m, 1) known points
+static int tnn_plan(const char* who, int B, int n, int m, PointGridPlan* pl) {
     GAD_REQUIRE(B >= 0 && n >= 0 && m >= 0, GAD_ERR_SHAPE, "%s: negative size (B=%d n=%d m=%d)", who, B, n, m);
     GAD_REQUIRE((long long)m * 3 < (1ll << 31) && (long long)B * m < (1ll << 31) && (long long)B * n < (1ll << 31) && B <= 65535,
                 GAD_ERR_SHAPE, "%s: B=%d clouds of n=%d queries and m=%d known points overflows 32-bit indexing (or B > 65535)", who, B, n, m);
     GAD_REQUIRE(m >= 1 || (long long)B * n == 0, GAD_ERR_SHAPE, "%s: no known point (m=%d) for n=%d queries", who, m, n);
-    return bqg_plan(who, B, std::max(m, 1), 0, 1, pl);
+    return point_grid_plan(who, B, std::max(m, 1), pl);
 }
 
 extern "C" long long gad_three_nn_grid_workspace_bytes(int B, int n, int m) {
-    BqgPlan pl;
+    PointGridPlan pl;
     const int rc = tnn_plan("three_nn_grid_workspace_bytes", B, n, m, &pl);
     return rc != GAD_OK ? rc : pl.total;
 }
@@ -1991,12 +1705,13 @@ extern "C" long long gad_three_nn_grid_workspace_bytes(int B, int n, int m) {
 extern "C" int gad_three_nn_grid(const float* unknown, const float* known, int B, int n, int m, float* dist2, int32_t* idx,
                                  int32_t* stats, void* workspace, void* stream) {
     GAD_REQUIRE(unknown && known && dist2 && idx, GAD_ERR_NULL, "three_nn_grid: null pointer (unknown / known / dist2 / idx)");
-    BqgPlan pl;
-    const int rc = tnn_plan("three_nn_grid", B, n, m, &pl);
+    PointGridPlan pl;
+    int rc = tnn_plan("three_nn_grid", B, n, m, &pl);
     if (rc != GAD_OK) return rc;
     if ((long long)B * n == 0) return GAD_OK;
-    GAD_REQUIRE(workspace, GAD_ERR_NULL, "three_nn_grid: null pointer (workspace)");
-    GAD_REQUIRE((reinterpret_cast<size_t>(workspace) & 7) == 0, GAD_ERR_SHAPE, "three_nn_grid: the workspace must be 8-byte aligned");
+    PointGridView v;
+    rc = point_grid_carve("three_nn_grid", workspace, pl, &v);
+    if (rc != GAD_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (!g_opt_tnn_grid) {
         const int tiles = gad_cdiv(n, 256);
@@ -2005,28 +1720,11 @@ extern "C" int gad_three_nn_grid(const float* unknown, const float* known, int B
         GAD_CHECK_LAUNCH("three_nn_grid(exhaustive)");
         return GAD_OK;
     }
-    char* w = static_cast<char*>(workspace);
-    float* part = reinterpret_cast<float*>(w);
-    BqgGrid* hdr = reinterpret_cast<BqgGrid*>(w + pl.o_hdr);
-    int32_t* cellof = reinterpret_cast<int32_t*>(w + pl.o_cellof);
-    int32_t* rank = reinterpret_cast<int32_t*>(w + pl.o_rank);
-    int32_t* table = reinterpret_cast<int32_t*>(w + pl.o_table);
-    int32_t* start = reinterpret_cast<int32_t*>(w + pl.o_start);
-    float4* sorted = reinterpret_cast<float4*>((reinterpret_cast<size_t>(w + pl.o_sorted) + 15) & ~(size_t)15);
-    const int pt_grid = (int)std::min<long long>(1024, gad_cdiv(m, 256));
     // a wavefront takes a run of per_wave queries of one cloud: about TNN_WAVES_TARGET wavefronts, one query each below that
     const int per_wave = (int)std::max<long long>(1, gad_cdiv((long long)B * n, TNN_WAVES_TARGET));
-    hipLaunchKernelGGL(bqg_bounds_kernel, dim3(pl.parts, B), dim3(256), 0, st, known, m, part, table,
-                       (long long)B * pl.slices * pl.cells);
-    hipLaunchKernelGGL(tnn_setup_kernel, dim3(B), dim3(64), 0, st, part, pl.parts, pl.cells, hdr, stats);
-    hipLaunchKernelGGL(bqg_count_kernel, dim3(B * pl.slices), dim3(64), 0, st, known, m, pl.slices, pl.slice, pl.cells, hdr, cellof, rank,
-                       table);
-    hipLaunchKernelGGL(bqg_slices_kernel, dim3(gad_cdiv(pl.cells, 256), B), dim3(256), 0, st, pl.slices, pl.cells, hdr, table, start);
-    hipLaunchKernelGGL(bqg_scan_kernel, dim3(B), dim3(1024), 0, st, m, pl.cells, hdr, start);
-    hipLaunchKernelGGL(bqg_scatter_kernel, dim3(pt_grid, B), dim3(256), 0, st, known, m, pl.slices, pl.slice, pl.cells, cellof, rank, table,
-                       start, sorted);
+    point_grid_build(known, B, m, pl, v, PG_EDGE_BUDGET, 0.f, stats, st);
     hipLaunchKernelGGL(tnn_query_kernel, dim3(gad_cdiv(gad_cdiv(n, per_wave), 4), B), dim3(256), 0, st, unknown, known, n, m, per_wave,
-                       pl.cells, hdr, start, sorted, dist2, idx, stats);
+                       pl.cells, v.hdr, v.start, v.sorted, dist2, idx, stats);
     GAD_CHECK_LAUNCH("three_nn_grid");
     return GAD_OK;
 }

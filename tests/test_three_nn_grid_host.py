@@ -83,6 +83,9 @@ def test_workspace_bytes():
             # the arrays the header names: box partials, grid header, cell + rank, slice counts, cell starts, sorted points
             assert per_n[0] >= B * (parts * 24 + 64 + m * 8 + slices * cells * 4 + (cells + 1) * 4 + m * 16)
             assert per_n[0] >= B * m * 24
+            # one grid, one layout: the ball query's workspace over the same cloud, whatever its centroids and nsample
+            bq = L.gad_ball_query_grid_workspace_bytes
+            assert all(bq(B, m, M, ns) == per_n[0] for M, ns in ((0, 1), (1, 16), (4096, 64), (16384, 200)))
             prev = per_n[0]
     assert ws(3, 64, 70000) >= ws(1, 64, 70000)
     assert ws(256, 64, 1 << 22) > 1 << 32                               # the size needs more than 32 bits before the shape does

@@ -1,10 +1,13 @@
-// Stand-alone check of the host side of gad_fps_tiled (include/gaddpg.h section A) for a sanitizer build: the workspace size and
-// every refusing argument path, none of which launches anything -- so it runs on a machine without a GPU.  Build it together
+// Stand-alone check of the host side of gad_fps_tiled, gad_ball_query_grid and gad_three_nn_grid (include/gaddpg.h section A) for a
+// sanitizer build: the workspace sizes, every refusing argument path and the calls with nothing to do, none of which launches
+// anything -- so it runs on a machine without a GPU.  (The expectations on the two grid entry points are those of
+// tests/test_ball_query_grid_host.py and tests/test_three_nn_grid_host.py.)  Build it together
 // with the library's sources, host code instrumented, and run it as it is:
 //
 //   cd ga-ddpg_amd/csrc && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -I../../include -munsafe-fp-atomics \
 //       -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
-//       ../../tools/fps_tiled_host_check.cpp geometry.hip gemm.hip layers.hip losses.hip optim.hip plan.hip -o fps_tiled_host_check
+//       ../../tools/fps_tiled_host_check.cpp geometry.hip point_grid.hip gemm.hip layers.hip losses.hip optim.hip plan.hip \
+//       -o fps_tiled_host_check
 //
 // Exit status 0 and "ok" on success; a failed expectation prints its line and exits 1.
 #include <stdio.h>
@@ -57,6 +60,72 @@ int main() {
     // the one-workgroup entry point's refusals, for comparison (unchanged)
     EXPECT(gad_furthest_point_sampling(p, 1, 64, 65, q, nullptr, nullptr) == GAD_ERR_SHAPE);
     EXPECT(gad_furthest_point_sampling(p, 1, 16384, 16384, q, nullptr, nullptr) == GAD_ERR_SHAPE);
+
+    // gad_ball_query_grid(new_xyz, xyz, B, N, M, radius, nsample, idx, cnt, workspace, stream)
+    auto bq = [&](const float* c, const float* x, int B, int N, int M, int ns, int32_t* idx, void* w) {
+        return gad_ball_query_grid(c, x, B, N, M, 0.1f, ns, idx, nullptr, w, nullptr);
+    };
+    auto says = [](const char* what) { return strstr(gad_last_error(), what) != nullptr; };
+    void* odd = reinterpret_cast<void*>(0x3004);
+    EXPECT(bq(nullptr, p, 1, 5000, 8, 4, q, ws) == GAD_ERR_NULL && says("null pointer"));
+    EXPECT(bq(p, nullptr, 1, 5000, 8, 4, q, ws) == GAD_ERR_NULL && says("null pointer"));
+    EXPECT(bq(p, p, 1, 5000, 8, 4, nullptr, ws) == GAD_ERR_NULL && says("null pointer"));
+    EXPECT(bq(p, p, 1, 5000, 8, 4, q, nullptr) == GAD_ERR_NULL && says("workspace"));
+    EXPECT(bq(p, p, 1, 5000, 8, 4, q, odd) == GAD_ERR_SHAPE && says("aligned"));
+    EXPECT(bq(p, p, -1, 5000, 8, 4, q, ws) == GAD_ERR_SHAPE && says("B=-1"));
+    EXPECT(bq(p, p, 1, 0, 8, 4, q, ws) == GAD_ERR_SHAPE && says("N=0"));
+    EXPECT(bq(p, p, 1, -3, 8, 4, q, ws) == GAD_ERR_SHAPE && says("N=-3"));
+    EXPECT(bq(p, p, 1, 5000, -2, 4, q, ws) == GAD_ERR_SHAPE && says("M=-2"));
+    EXPECT(bq(p, p, 1, 5000, 8, 0, q, ws) == GAD_ERR_SHAPE && says("nsample=0"));
+    EXPECT(bq(p, p, 1, 5000, 8, -1, q, ws) == GAD_ERR_SHAPE && says("nsample=-1"));
+    EXPECT(bq(p, p, 1, 800000000, 8, 4, q, ws) == GAD_ERR_SHAPE && says("overflows"));      // 3 * N, B * N, the grid of B * M centroids
+    EXPECT(bq(p, p, 1024, 1 << 21, 8, 4, q, ws) == GAD_ERR_SHAPE && says("overflows"));
+    EXPECT(bq(p, p, 1 << 10, 5000, 1 << 16, 4, q, ws) == GAD_ERR_SHAPE && says("overflows"));
+    EXPECT(bq(p, p, 0, 5000, 8, 4, q, nullptr) == GAD_OK);                                    // nothing to search: no launch
+    EXPECT(bq(p, p, 2, 5000, 0, 4, q, nullptr) == GAD_OK);
+    EXPECT(gad_ball_query_grid_workspace_bytes(1, 5000, 8, 16) >= 5000 * 24);
+    EXPECT(gad_ball_query_grid_workspace_bytes(3, 70000, 64, 200) >= gad_ball_query_grid_workspace_bytes(1, 70000, 64, 200));
+    EXPECT(gad_ball_query_grid_workspace_bytes(256, 1 << 22, 64, 16) > 1ll << 32);          // more than 32 bits before the shape is
+    EXPECT(gad_ball_query_grid_workspace_bytes(1, 0, 8, 4) == GAD_ERR_SHAPE && says("N=0"));
+    EXPECT(gad_ball_query_grid_workspace_bytes(-1, 64, 8, 4) == GAD_ERR_SHAPE && says("B=-1"));
+    EXPECT(gad_ball_query_grid_workspace_bytes(1, 64, 8, 0) == GAD_ERR_SHAPE && says("nsample=0"));
+    EXPECT(gad_ball_query_grid_workspace_bytes(1, 800000000, 8, 4) == GAD_ERR_SHAPE && says("overflows"));
+    EXPECT(gad_ball_query_grid_workspace_bytes(1 << 10, 5000, 1 << 16, 4) == GAD_ERR_SHAPE && says("overflows"));
+
+    // gad_three_nn_grid(unknown, known, B, n, m, dist2, idx, stats, workspace, stream)
+    auto nn = [&](const float* u, const float* k, int B, int n, int m, float* d, int32_t* idx, void* w) {
+        return gad_three_nn_grid(u, k, B, n, m, d, idx, nullptr, w, nullptr);
+    };
+    EXPECT(nn(nullptr, p, 1, 8, 5000, p, q, ws) == GAD_ERR_NULL && says("null pointer"));
+    EXPECT(nn(p, nullptr, 1, 8, 5000, p, q, ws) == GAD_ERR_NULL && says("null pointer"));
+    EXPECT(nn(p, p, 1, 8, 5000, nullptr, q, ws) == GAD_ERR_NULL && says("null pointer"));
+    EXPECT(nn(p, p, 1, 8, 5000, p, nullptr, ws) == GAD_ERR_NULL && says("null pointer"));
+    EXPECT(nn(p, p, 1, 8, 5000, p, q, nullptr) == GAD_ERR_NULL && says("workspace"));
+    EXPECT(nn(p, p, 1, 8, 5000, p, q, odd) == GAD_ERR_SHAPE && says("aligned"));
+    EXPECT(nn(p, p, -1, 8, 5000, p, q, ws) == GAD_ERR_SHAPE && says("B=-1"));
+    EXPECT(nn(p, p, 1, -8, 5000, p, q, ws) == GAD_ERR_SHAPE && says("n=-8"));
+    EXPECT(nn(p, p, 1, 8, -3, p, q, ws) == GAD_ERR_SHAPE && says("m=-3"));
+    EXPECT(nn(p, p, 1, 8, 0, p, q, ws) == GAD_ERR_SHAPE && says("no known point"));
+    EXPECT(nn(p, p, 1, 8, 800000000, p, q, ws) == GAD_ERR_SHAPE && says("overflows"));       // 3 * m, B * m, B * n, B itself
+    EXPECT(nn(p, p, 1024, 8, 1 << 21, p, q, ws) == GAD_ERR_SHAPE && says("overflows"));
+    EXPECT(nn(p, p, 1024, 1 << 21, 64, p, q, ws) == GAD_ERR_SHAPE && says("overflows"));
+    EXPECT(nn(p, p, 65536, 8, 64, p, q, ws) == GAD_ERR_SHAPE && says("65535"));
+    EXPECT(nn(p, p, 0, 8, 5000, p, q, nullptr) == GAD_OK);                                    // no query: no launch, and m may be 0
+    EXPECT(nn(p, p, 2, 0, 5000, p, q, nullptr) == GAD_OK);
+    EXPECT(gad_three_nn_grid(p, p, 2, 0, 0, p, q, q, nullptr, nullptr) == GAD_OK);
+    EXPECT(gad_three_nn_grid_workspace_bytes(1, 0, 5000) == gad_three_nn_grid_workspace_bytes(1, 1 << 20, 5000));
+    EXPECT(gad_three_nn_grid_workspace_bytes(1, 8, 5000) == gad_ball_query_grid_workspace_bytes(1, 5000, 8, 16));   // one grid, one layout
+    EXPECT(gad_three_nn_grid_workspace_bytes(3, 64, 70000) >= gad_three_nn_grid_workspace_bytes(1, 64, 70000));
+    EXPECT(gad_three_nn_grid_workspace_bytes(256, 64, 1 << 22) > 1ll << 32);
+    EXPECT(gad_three_nn_grid_workspace_bytes(1, 8, 0) == GAD_ERR_SHAPE && says("no known point"));
+    EXPECT(gad_three_nn_grid_workspace_bytes(-1, 8, 64) == GAD_ERR_SHAPE && says("B=-1"));
+    EXPECT(gad_three_nn_grid_workspace_bytes(1, -8, 64) == GAD_ERR_SHAPE && says("n=-8"));
+    EXPECT(gad_three_nn_grid_workspace_bytes(1, 8, -64) == GAD_ERR_SHAPE && says("m=-64"));
+    EXPECT(gad_three_nn_grid_workspace_bytes(1, 8, 800000000) == GAD_ERR_SHAPE && says("overflows"));
+    EXPECT(gad_three_nn_grid_workspace_bytes(1024, 8, 1 << 21) == GAD_ERR_SHAPE && says("overflows"));
+    EXPECT(gad_three_nn_grid_workspace_bytes(1024, 1 << 21, 64) == GAD_ERR_SHAPE && says("overflows"));
+    EXPECT(gad_three_nn_grid_workspace_bytes(65536, 8, 64) == GAD_ERR_SHAPE && says("65535"));
+    EXPECT(gad_three_nn_grid_workspace_bytes(2, 0, 0) > 0);                                   // nothing to search is no error
     if (g_failed) return 1;
     printf("ok\n");
     return 0;
