@@ -3684,6 +3684,9 @@ extern "C" int gad_gemm_dx(const gad_gemm_dx_args* a, void* stream) {
     GAD_REQUIRE(a->n_groups >= 1 && a->n_groups <= GAD_MAX_GROUPS, GAD_ERR_SHAPE, "gemm_dx: n_groups");
     GAD_REQUIRE(a->Kp % 8 == 0, GAD_ERR_SHAPE, "gemm_dx: Kp must be a multiple of 8");
     GAD_REQUIRE(a->epilogue == 1 || a->gout, GAD_ERR_NULL, "gemm_dx: gout");
+    // every group STORES its own gout columns: no kernel adds the groups of one launch into shared columns
+    GAD_REQUIRE(a->accumulate == 0 || a->n_groups == 1, GAD_ERR_UNSUPPORTED, "gemm_dx: accumulate=%d with %d groups is not implemented "
+                "(groups store, they do not add: concatenate the groups into one, or give each its own gout_off)", a->accumulate, a->n_groups);
     GAD_REQUIRE(a->dz.gmode == 0 ? a->dz.G != nullptr : (a->dz.argmax && a->dz.dout && a->dz.row_grp), GAD_ERR_NULL,
                 "gemm_dx: gradient source");
     if (a->n_rows <= 0) return GAD_OK;

@@ -516,7 +516,10 @@ typedef struct {
     int32_t w_off[GAD_MAX_GROUPS];
     int32_t n_out[GAD_MAX_GROUPS];
     int32_t gout_off[GAD_MAX_GROUPS];/* channel offset into gout                                  */
-    int32_t accumulate;              /* groups add into the same gout columns (shared input)      */
+    int32_t accumulate;              /* reserved: groups adding into the same gout columns (shared input) is NOT implemented --
+                                      * every group stores its own columns [gout_off, gout_off + k_valid).  Must be 0 with more
+                                      * than one group (GAD_ERR_UNSUPPORTED otherwise); ignored with one group.  A layer whose
+                                      * groups share their input runs as one concatenated group instead (the critic's first) */
     const float* W;
     int32_t Kp;
     int32_t k_valid;                 /* input channels to produce (columns >= k_valid are skipped)*/

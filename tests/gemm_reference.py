@@ -1,0 +1,182 @@
+"""Plain references for the layer GEMMs of ga-ddpg_amd/csrc/gemm.hip (gad_gemm_fwd / gad_gemm_dx / gad_gemm_dw), written from
+include/gaddpg.h.  torch only, no GPU needed: every function runs on CPU tensors as well as on device tensors, and in the dtype of
+its inputs -- float32 inputs give the OPERANDS exactly as the kernels form them (one rounding per fused multiply-add, float32
+subtraction of the gathered coordinates), products and sums are float64 throughout; float64 inputs give the operation itself, which
+tests/test_gemm_reference.py pins to torch autograd.
+
+Layouts (include/gaddpg.h section C): W is the flat packed weight buffer, group g's matrix (n_out[g], Kp) row-major at element
+w_off[g]; activations are (rows, channels) row-major; a per-channel vector (scale, shift, P, Q, S) is indexed by the channel
+inside the full row, i.e. at the group's offset + the local channel."""
+import torch
+
+
+def fma32(z, s, t):
+    """fmaf(z, s, t) as the kernels evaluate it: one rounding (the float64 product is exact, the float64 sum exact enough);
+    float64 inputs: z * s + t"""
+    if z.dtype == torch.float32:
+        return (z.double() * s.double() + t.double()).float()
+    return z * s + t
+
+
+# ----------------------------------------------------------------------------- forward operand A
+def act_operand(zin, zin_off, c_in, Kp, scale=None, shift=None, relu=0, extra=None, ones_col=-1, rows=None):
+    """ACT input of one group -> (rows, Kp): columns [0, c_in) = relu?(fma(z, scale, shift)) of zin[:, zin_off : zin_off + c_in]
+    (scale None: identity), 1.0 at ones_col, the extra column at c_in (it wins over ones_col == c_in, as in x_raw), 0 elsewhere"""
+    r = zin.shape[0] if rows is None else rows
+    x = zin[:r, zin_off:zin_off + c_in]
+    if scale is not None:
+        x = fma32(x, scale[zin_off:zin_off + c_in], shift[zin_off:zin_off + c_in])
+    if relu:
+        x = x.clamp_min(0)
+    A = torch.zeros(r, Kp, dtype=zin.dtype, device=zin.device)
+    A[:, :c_in] = x
+    if ones_col >= 0:
+        A[:, ones_col] = 1
+    if extra is not None:
+        A[:, c_in] = extra[:r]
+    return A
+
+
+def gather_operand(feat, src_xyz, ctr_xyz, action, row_pt, row_grp, grp_per_sample, Kp, rows=None):
+    """GATHER input -> (rows, Kp): [feat[pt] | src_xyz[pt] - ctr_xyz[grp] (subtraction in the input dtype; ctr_xyz None: no
+    recentring) | action[grp // grp_per_sample] (action None: absent) | 0 ...]"""
+    r = row_pt.shape[0] if rows is None else rows
+    pt, grp = row_pt[:r].long(), row_grp[:r].long()
+    dx = src_xyz[pt] if ctr_xyz is None else src_xyz[pt] - ctr_xyz[grp]
+    parts = [feat[pt], dx]
+    if action is not None:
+        parts.append(action[torch.div(grp, max(int(grp_per_sample), 1), rounding_mode="floor")])
+    x = torch.cat(parts, 1)
+    A = torch.zeros(r, Kp, dtype=feat.dtype, device=feat.device)
+    A[:, :x.shape[1]] = x
+    return A
+
+
+# ----------------------------------------------------------------------------- the gate's magnitudes
+def abs_bound(A, W):
+    """|A| @ |W|^T in float64: the sum of |terms| behind every element of A @ W^T"""
+    return A.double().abs() @ W.double().abs().t()
+
+
+def abs_bound_dx(dZ, W):
+    """|dZ| @ |W| in float64 (gout = dZ @ W)"""
+    return dZ.double().abs() @ W.double().abs()
+
+
+def abs_bound_dw(dZ, A):
+    """|dZ|^T @ |A| in float64 (dW = dZ^T @ A)"""
+    return dZ.double().abs().t() @ A.double().abs()
+
+
+def _mat(W, off, n, Kp):
+    return W.reshape(-1)[off:off + n * Kp].view(n, Kp)
+
+
+# ----------------------------------------------------------------------------- forward outputs
+def forward(As, W, Kp, w_off, out_off, n_out, width, k_used=None, row_w=None):
+    """gad_gemm_fwd.  As: the operand of every group (rows, Kp).  -> float64 dict:
+    z (rows, width): A @ W[:, :k_used]^T of every group at its out_off, NaN where no group writes; stat_sum / stat_sq (width):
+    sum_r w * z, sum_r w * z^2 (0 where no group writes); "#abs" companions: z#abs = |A| @ |W|^T, stat_sum#abs = sum_r w * z#abs,
+    stat_sq#abs = sum_r w * z#abs^2 (what the rounding errors of the float32 evaluation are relative to)"""
+    rows = As[0].shape[0]
+    dev = As[0].device
+    k_used = Kp if k_used is None else k_used
+    z = torch.full((rows, width), float("nan"), dtype=torch.float64, device=dev)
+    za = torch.zeros(rows, width, dtype=torch.float64, device=dev)
+    for A, wo, oo, n in zip(As, w_off, out_off, n_out):
+        Wg = _mat(W, wo, n, Kp)[:, :k_used]
+        z[:, oo:oo + n] = A[:, :k_used].double() @ Wg.double().t()
+        za[:, oo:oo + n] = abs_bound(A[:, :k_used], Wg)
+    w = torch.ones(rows, 1, dtype=torch.float64, device=dev) if row_w is None else row_w[:rows].double()[:, None]
+    zz = torch.nan_to_num(z, nan=0.0)
+    return {"z": z, "z#abs": za, "stat_sum": (w * zz).sum(0), "stat_sq": (w * zz * zz).sum(0), "stat_sum#abs": (w * za).sum(0),
+            "stat_sq#abs": (w * za * za).sum(0)}
+
+
+# ----------------------------------------------------------------------------- backward operand dZ
+def route_pooled(argmax, dout, row_grp, rows):
+    """dense dY (rows, C) of a pooled gradient source: dout[grp] where the group's arg-max row is this row, else 0"""
+    grp = row_grp[:rows].long()
+    rowid = torch.arange(rows, device=dout.device, dtype=argmax.dtype)[:, None]
+    return torch.where(argmax[grp] == rowid, dout[grp], torch.zeros((), dtype=dout.dtype, device=dout.device))
+
+
+def dz_operand(g, z=None, scale=None, shift=None, relu=0, premasked=0, P=None, Q=None, S=None, row_w=None):
+    """dZ = P * dY - w * (Q + S * z) over the layer's full channel width, in the dtype of g.  dY = g, zeroed where the layer's own
+    activation fma(z, scale, shift) (scale None: z) is not positive when relu and not premasked.  P None: dZ = dY.
+    float32: P * dY and w * fma(S, z, Q) in float64 and ONE rounding of their difference -- what the kernels give, however the compiler
+    contracts the expression, when P and w are powers of two (the cases' device-side trick)."""
+    rows = g.shape[0]
+    if relu and not premasked:
+        y = z[:rows] if scale is None else fma32(z[:rows], scale, shift)
+        g = torch.where(y > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
+    if P is None:
+        return g
+    w = torch.ones(rows, 1, dtype=g.dtype, device=g.device) if row_w is None else row_w[:rows][:, None]
+    inner = fma32(z[:rows], S, Q)
+    return (P.double() * g.double() - w.double() * inner.double()).to(g.dtype)
+
+
+# ----------------------------------------------------------------------------- backward outputs
+def dx(dZ, W, Kp, k_valid, dz_off, w_off, n_out, gout_off, width, prev=None, store_masked=0):
+    """gad_gemm_dx, epilogue 0.  dZ: (rows, C) operand.  prev: None, or the previous layer's dict(zprev, scale, shift, mean, istd)
+    indexed like gout.  -> float64 dict: gx (rows, width) = dZ[:, dz_off : + n_out] @ W[:, :k_valid] of every group at its
+    gout_off (NaN where no group writes); gout = gx, with store_masked zeroed where the previous layer's activation
+    fma(zprev, scale, shift) is not positive; dbeta = sum over the rows of gx where it is positive, dgamma = the same sum of
+    gx * (zprev - mean) * istd; "#abs" companions from |dZ| @ |W|"""
+    rows = dZ.shape[0]
+    dev = dZ.device
+    gx = torch.full((rows, width), float("nan"), dtype=torch.float64, device=dev)
+    ga = torch.zeros(rows, width, dtype=torch.float64, device=dev)
+    for do, wo, n, go in zip(dz_off, w_off, n_out, gout_off):
+        Wg = _mat(W, wo, n, Kp)[:, :k_valid]
+        gx[:, go:go + k_valid] = dZ[:, do:do + n].double() @ Wg.double()
+        ga[:, go:go + k_valid] = abs_bound_dx(dZ[:, do:do + n], Wg)
+    out = {"gx": gx, "gout": gx, "gout#abs": ga}
+    if prev is not None:
+        zp = prev["zprev"][:rows, :width]
+        live = fma32(zp, prev["scale"][:width], prev["shift"][:width]) > 0
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        g0 = torch.nan_to_num(gx, nan=0.0)
+        m = torch.where(live, g0, zero)
+        xhat = (zp.double() - prev["mean"][:width].double()) * prev["istd"][:width].double()
+        out.update({"dbeta": m.sum(0), "dgamma": (m * xhat).sum(0), "dbeta#abs": torch.where(live, ga, zero).sum(0),
+                    "dgamma#abs": (torch.where(live, ga, zero) * xhat.abs()).sum(0)})
+        if store_masked:
+            out["gout"] = torch.where(live | torch.isnan(gx), gx, zero)
+    return out
+
+
+def scatter(gx, gabs, row_pt, row_grp, grp_per_sample, feat_c, act_c, n_points, n_samples):
+    """gad_gemm_dx, epilogue 1 (gx / gabs: the raw product of one group at gout_off 0 and its |terms|): dfeat (n_points, feat_c)
+    += columns [0, feat_c) by point through index_add_; daction (n_samples, act_c) += columns [feat_c + 3, feat_c + 3 + act_c) by
+    sample row_grp // grp_per_sample"""
+    rows = gx.shape[0]
+    pt = row_pt[:rows].long()
+    smp = torch.div(row_grp[:rows].long(), max(int(grp_per_sample), 1), rounding_mode="floor")
+    out = {}
+    for key, src in (("", gx), ("#abs", gabs)):
+        f = torch.zeros(n_points, feat_c, dtype=torch.float64, device=gx.device)
+        f.index_add_(0, pt, src[:, :feat_c])
+        out["dfeat" + key] = f
+        if act_c > 0:
+            a = torch.zeros(n_samples, act_c, dtype=torch.float64, device=gx.device)
+            a.index_add_(0, smp, src[:, feat_c + 3:feat_c + 3 + act_c])
+            out["daction" + key] = a
+    return out
+
+
+def dw(dZ, As, Kp, k_used, dz_off, w_off, n_out, total):
+    """gad_gemm_dw: what the call ADDS to the flat f64 arena of `total` elements -- group g's (n_out, Kp) block at w_off[g] receives
+    dZ[:, dz_off : + n_out]^T @ A_g[:, :k_used] in its first k_used columns, nothing else is touched.
+    -> float64 dict: dW (total), dW#abs, dW#mask (bool: the words the call may write)"""
+    dev = dZ.device
+    out = torch.zeros(total, dtype=torch.float64, device=dev)
+    ab = torch.zeros(total, dtype=torch.float64, device=dev)
+    mask = torch.zeros(total, dtype=torch.bool, device=dev)
+    for A, do, wo, n in zip(As, dz_off, w_off, n_out):
+        d = dZ[:, do:do + n]
+        _mat(out, wo, n, Kp)[:, :k_used] = d.double().t() @ A[:, :k_used].double()
+        _mat(ab, wo, n, Kp)[:, :k_used] = abs_bound_dw(d, A[:, :k_used])
+        _mat(mask, wo, n, Kp)[:, :k_used] = True
+    return {"dW": out, "dW#abs": ab, "dW#mask": mask}
