@@ -143,7 +143,12 @@ class Agent(object):
         from ..runtime import feature_forward
         self.state_feature_extractor.eval()
         self.policy.eval()
-        pc = torch.as_tensor(np.asarray(state[0][0], dtype=np.float32)[None]).cuda()
+        s0 = state[0][0]
+        if torch.is_tensor(s0) and s0.is_cuda and s0.dtype == torch.float32:
+            # a device-resident state (core.point_state.PointStateBuilder.observe): consumed as it is, no host round trip
+            pc = (s0[None] if s0.dim() == 2 else s0).contiguous()
+        else:
+            pc = torch.as_tensor(np.asarray(s0, dtype=np.float32)[None]).cuda()
         z = feature_forward(self.state_feature_extractor.module, pc, value=False)
         feat = torch.cat((z, torch.full((1, 1), float(remain_timestep), device=z.device)), dim=1)
         if eps is not None:

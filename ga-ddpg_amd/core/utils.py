@@ -3,7 +3,9 @@ reference's names (reference core/utils.py: make_nets_opts_schedulers :183-237, 
 :240-241, concat_state_action_channelwise :291-297, PandaTaskSpace6D :505-510, get_noise_delta
 :568-584, soft/half-soft/half-hard/hard updates :750-774, get_policy_class :960-981, get_critic
 :984-1006, get_loss_info_dict :1008-1020, module_max_param/gradient :92-108).
-Everything env/vision related in the reference's utils.py is out of scope."""
+The observation helpers se3_transform_pc :308-314 and backproject_camera_target[_realworld] :454-491 keep the reference's
+signatures over the device operators of core.point_state; everything else env/vision related in the reference's utils.py is out
+of scope."""
 from collections import deque
 
 import numpy as np
@@ -240,3 +242,37 @@ def regularize_pc_point_count(pc, npoints, use_farthest_point=False):
         extra = np.random.choice(range(n), size=npoints - n)
         return np.concatenate((pc, pc[extra, :]), axis=0)
     return pc
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# observation helpers with the reference's signatures (numpy in, float32 numpy out), computed by the device operators of
+# core.point_state -- regularize_pc_point_count above is the precedent.  A rollout loop uses PointStateBuilder instead: it
+# keeps the cloud on the device.
+# ---------------------------------------------------------------------------------------------------------------------
+def se3_transform_pc(pose, point):
+    """pose[:3, :3] . point[:3] + pose[:3, [3]] for a (C, n) cloud, rows beyond the third passed through (reference
+    core/utils.py:308-314); float32 result"""
+    from .point_state import cloud_gather_affine, pose_affine
+    out = np.array(point, dtype=np.float32)
+    xyz = torch.from_numpy(np.ascontiguousarray(out[:3].T)).cuda()
+    out[:3] = cloud_gather_affine(xyz, None, pose_affine(pose))[0].cpu().numpy().T
+    return out
+
+
+def _backproject(im_depth, K, target_mask, flip_y):
+    from .point_state import backproject_depth, compose_camera_affine
+    depth = torch.from_numpy(np.ascontiguousarray(im_depth, dtype=np.float32)).cuda()[None]
+    mask = torch.from_numpy(np.ascontiguousarray(np.asarray(target_mask) != 0, dtype=np.uint8)).cuda().reshape(depth.shape)
+    xyz, count, _ = backproject_depth(depth, mask, compose_camera_affine(K, None, flip_y)[None], want_pix=False)
+    return xyz[0, :int(count.item())].cpu().numpy().T
+
+
+def backproject_camera_target(im_depth, K, target_mask):
+    """(H, W) depth, 3x3 intrinsics, (H, W) mask -> (3, n) float32 camera-frame points of the pixels with depth != 0 and
+    mask == 0, in ascending pixel order, y flipped (OpenGL; reference core/utils.py:454-472)"""
+    return _backproject(im_depth, K, target_mask, True)
+
+
+def backproject_camera_target_realworld(im_depth, K, target_mask):
+    """the same without the y flip (reference core/utils.py:474-491)"""
+    return _backproject(im_depth, K, target_mask, False)

@@ -93,6 +93,9 @@ const std::vector<reg_entry>& registry() {
         GAD_PLAN_ENTRY(gad_three_interpolate)
         GAD_PLAN_ENTRY(gad_three_interpolate_grad)
         GAD_PLAN_ENTRY(gad_query_and_group)
+        GAD_PLAN_ENTRY(gad_backproject_depth)
+        GAD_PLAN_ENTRY(gad_cloud_gather_affine)
+        GAD_PLAN_ENTRY(gad_point_state_pack)
         GAD_PLAN_ENTRY(gad_prep_points)
         GAD_PLAN_ENTRY(gad_rows_from_ball_query)
         GAD_PLAN_ENTRY(gad_rows_group_all)

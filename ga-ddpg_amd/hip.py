@@ -152,6 +152,7 @@ EXPORTS = (
     "gad_gather_points_grad", "gad_ball_query", "gad_ball_query_grid_workspace_bytes", "gad_ball_query_grid",
     "gad_group_points", "gad_group_points_grad",
     "gad_three_nn", "gad_three_nn_grid_workspace_bytes", "gad_three_nn_grid", "gad_three_interpolate", "gad_three_interpolate_grad",
+    "gad_backproject_depth_workspace_bytes", "gad_backproject_depth", "gad_cloud_gather_affine", "gad_point_state_pack",
     "gad_query_and_group", "gad_prep_points", "gad_rows_from_ball_query", "gad_rows_group_all",
     "gad_gemm_fwd", "gad_bn_finalize", "gad_bn_eval_affine", "gad_segment_pool", "gad_pool_finalize", "gad_affine_act", "gad_transpose_batched",
     "gad_pool_bwd_stats", "gad_bn_bwd_coef", "gad_gemm_dx", "gad_gemm_dw", "gad_gemm_bwd", "gad_gemm_dw_reduce", "gad_critic_loss",
@@ -163,7 +164,7 @@ EXPORTS = (
     "gad_plan_entry_count", "gad_plan_entry_name")
 
 
-# argument types of the feature-propagation, tiled-sampling and grid-search entry points (include/gaddpg.h section A), set when the library
+# argument types of the feature-propagation, tiled-sampling, grid-search and observation entry points (include/gaddpg.h section A), set when the library
 # loads: ctypes then refuses a call whose argument count or kinds do not match
 _SIGNATURES = {
     "gad_fps_tiled_workspace_bytes": [C.c_int, C.c_int, C.c_int, C.c_int],
@@ -175,12 +176,16 @@ _SIGNATURES = {
     "gad_three_nn_grid": [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp],
     "gad_three_interpolate": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
     "gad_three_interpolate_grad": [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp],
+    "gad_backproject_depth_workspace_bytes": [C.c_int, C.c_int, C.c_int],
+    "gad_backproject_depth": [_vp, C.c_int, C.c_float, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp],
+    "gad_cloud_gather_affine": [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp],
+    "gad_point_state_pack": [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_float, C.c_int, C.c_int, _vp, _vp],
 }
 
 
 # every other entry point returns an int status
 _RESTYPES = {"gad_fps_tiled_workspace_bytes": C.c_longlong, "gad_ball_query_grid_workspace_bytes": C.c_longlong,
-             "gad_three_nn_grid_workspace_bytes": C.c_longlong}
+             "gad_three_nn_grid_workspace_bytes": C.c_longlong, "gad_backproject_depth_workspace_bytes": C.c_longlong}
 
 
 def workspace(name, device, *shape):

@@ -62,7 +62,9 @@ int gad_abi_version(void);                 /* bumped on any signature change or 
                                             * gad_ball_query_grid_workspace_bytes, option "bq_grid" (additive: the radius
                                             * search through a uniform grid in global memory); gad_three_nn_grid and
                                             * gad_three_nn_grid_workspace_bytes, option "tnn_grid" (additive: three_nn
-                                            * through the same grid)                                                    */
+                                            * through the same grid); gad_backproject_depth,
+                                            * gad_backproject_depth_workspace_bytes, gad_cloud_gather_affine and
+                                            * gad_point_state_pack (additive: section A.2, depth frame -> point state)  */
 /* diagnostics: which kernel family the last gad_gemm_fwd / _dx / _dw / _bwd call routed to ("gemm_fwd(stream)",
  * "gemm_dx(wide)", "gemm_bwd(stream)", "gemm_dw" = generic tile kernel, ...); bench.py labels its per-kernel table
  * with it instead of restating the routing rules.                                                  */
@@ -278,6 +280,53 @@ int gad_three_interpolate_grad(const float* grad_out, const int32_t* idx, const 
 int gad_query_and_group(const float* new_xyz, const float* xyz, const float* features /*(B,C,N)*/,
                         int B, int C, int N, int M, float radius, int nsample, int32_t* idx,
                         float* out, void* stream);
+
+/* ---- A.2 observation: depth frame -> point state (reference core/utils.py:308-314, 454-491 and env/panda_scene.py:442-450,
+ * 698-714, 1178-1206, host numpy there).  Not operators of pointnet2_ops._ext: they stand in this section because they produce the
+ * clouds its operators consume.  An affine `A` is 12 floats, the rows of the 3 x 4 matrix [M | t]: A[4k .. 4k+2] = M[k][0..2],
+ * A[4k+3] = t_k (pose[:3, :4] of a 4 x 4 pose, flattened).
+ *
+ * gad_backproject_depth: depth (B,H,W) row-major, float32 metres (depth_u16 = 0; depth_div is ignored) or uint16 (depth_u16 = 1):
+ * d = (float)u / depth_div, one IEEE division (numpy's astype(float32) / 5000).  mask (B,H,W) uint8, nullable (nothing masked).
+ * A (B,12).  Pixel p = y * W + x of image b is KEPT iff d != 0 and mask == 0 -- a NaN depth compares unequal to 0 and is kept,
+ * as by the reference's test (utils.py:460).  Its point is
+ *   r_k = (M[k][0] * x + M[k][1] * y) + M[k][2],    P_k = d * r_k + t_k        (k = 0, 1, 2; x, y as float32, exact)
+ * in float32, every operation individually rounded, in that order (no FMA contraction).
+ * Outputs: xyz (B, H*W, 3): the kept points of image b, compacted to the front of its block in ascending pixel order -- the order
+ * of numpy's boolean mask X[:, mask] -- rows past the count are left untouched; count (B) i32; pix (B, H*W) i32, nullable: the
+ * source pixel p of every kept point, rows past the count untouched.  The compaction is stable and does not depend on scheduling:
+ * no atomic places a point.  The call enqueues three launches on `stream` (per-tile counts, one workgroup per image scanning its
+ * tile counts and writing count[b], scatter) ordered by the stream alone -- no workgroup waits for another inside a launch, no host
+ * synchronisation, no allocation.  The inputs must not change between the launches.  Nothing in the images is range-checked:
+ * any bit pattern is a legal depth (infinities and NaNs are kept and propagate), any non-zero mask byte masks.
+ * Limits: 1 <= H, W <= 4096; B >= 0; B * H * W within 2^31 and B * ceil(H*W / 1024) within 2^23; a uint16 depth needs a finite
+ * depth_div > 0; depth aligned to its element size (GAD_ERR_SHAPE otherwise, GAD_ERR_NULL for a null depth / A / xyz / count /
+ * workspace).  B == 0: GAD_OK without a launch (every pointer may then be NULL).
+ * Workspace contract as for gad_fps_tiled: caller-allocated DEVICE memory of at least gad_backproject_depth_workspace_bytes(B, H, W)
+ * bytes (one i32 per tile of 1024 pixels), 8-byte aligned, uninitialised on entry, owned by the call until its launches have run on
+ * `stream`, free to reuse afterwards; gad_backproject_depth_workspace_bytes applies the shape checks above and returns the negative
+ * gad_status where the call would refuse.                                                                                        */
+long long gad_backproject_depth_workspace_bytes(int B, int H, int W);
+int gad_backproject_depth(const void* depth, int depth_u16, float depth_div, const uint8_t* mask /*nullable*/, const float* A,
+                          int B, int H, int W, float* xyz, int32_t* count, int32_t* pix /*nullable*/, void* workspace,
+                          void* stream);
+/* gad_cloud_gather_affine: dst[b][j] = M_b . src[b][sel[b][j]] + t_b for j < n (se3_transform_pc of a subsample):
+ *   dst_k = ((M[k][0] * x + M[k][1] * y) + M[k][2] * z) + t_k
+ * in float32, every operation individually rounded, in that order.  src and dst are point-major (., 3); cloud b starts
+ * src_stride / dst_stride FLOATS after cloud b - 1, so a view into a larger buffer is valid for either.  sel (B,n) i32, nullable
+ * (identity: sel[b][j] = j); A (B,12), nullable (the points are copied bit for bit).  Indices are NOT range-checked (as in
+ * gad_group_points): the caller passes rows that exist in src.  src and dst must not overlap.  B * n == 0: GAD_OK without a launch
+ * (src / dst may then be NULL); a negative size or stride, or B * n beyond 2^31, is GAD_ERR_SHAPE.                               */
+int gad_cloud_gather_affine(const float* src, int src_stride, const int32_t* sel /*nullable*/, const float* A /*nullable*/, int B,
+                            int n, float* dst, int dst_stride, void* stream);
+/* gad_point_state_pack: the inverse of gad_prep_points.  state (B, 4, n_lead + n) channel-major f32 (rows x, y, z, flag):
+ * columns [0, n_lead) hold the lead points -- lead (n_lead,3) point-major, shared by every sample, copied bit for bit -- with flag
+ * lead_flag; column n_lead + j holds M_b . src[b][sel[b][j]] + t_b, src / src_stride / sel / A and the arithmetic as in
+ * gad_cloud_gather_affine, with flag 0.  Every element of state is written; stores are contiguous along the point axis.  n == 0
+ * writes the lead columns only (src may then be NULL); lead may be NULL when n_lead == 0 (GAD_ERR_NULL otherwise).
+ * B * (n_lead + n) == 0: GAD_OK without a launch; a negative size or stride, or B * (n_lead + n) beyond 2^31, is GAD_ERR_SHAPE. */
+int gad_point_state_pack(const float* src, int src_stride, const int32_t* sel /*nullable*/, const float* A /*nullable*/,
+                         const float* lead /*nullable*/, int n_lead, float lead_flag, int B, int n, float* state, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * B. geometry for the fused set-abstraction path (de-duplicated neighbourhood rows)

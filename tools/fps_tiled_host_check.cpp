@@ -1,12 +1,14 @@
-// Stand-alone check of the host side of gad_fps_tiled, gad_ball_query_grid and gad_three_nn_grid (include/gaddpg.h section A) for a
+// Stand-alone check of the host side of gad_fps_tiled, gad_ball_query_grid, gad_three_nn_grid and the observation entry points
+// (gad_backproject_depth, gad_cloud_gather_affine, gad_point_state_pack) (include/gaddpg.h section A) for a
 // sanitizer build: the workspace sizes, every refusing argument path and the calls with nothing to do, none of which launches
 // anything -- so it runs on a machine without a GPU.  (The expectations on the two grid entry points are those of
-// tests/test_ball_query_grid_host.py and tests/test_three_nn_grid_host.py.)  Build it together
+// tests/test_ball_query_grid_host.py and tests/test_three_nn_grid_host.py, those on the observation entry points of
+// tests/test_point_state_host.py.)  Build it together
 // with the library's sources, host code instrumented, and run it as it is:
 //
 //   cd ga-ddpg_amd/csrc && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -I../../include -munsafe-fp-atomics \
 //       -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
-//       ../../tools/fps_tiled_host_check.cpp geometry.hip point_grid.hip gemm.hip layers.hip losses.hip optim.hip plan.hip \
+//       ../../tools/fps_tiled_host_check.cpp geometry.hip point_grid.hip observe.hip gemm.hip layers.hip losses.hip optim.hip plan.hip \
 //       -o fps_tiled_host_check
 //
 // Exit status 0 and "ok" on success; a failed expectation prints its line and exits 1.
@@ -126,6 +128,52 @@ int main() {
     EXPECT(gad_three_nn_grid_workspace_bytes(1024, 1 << 21, 64) == GAD_ERR_SHAPE && says("overflows"));
     EXPECT(gad_three_nn_grid_workspace_bytes(65536, 8, 64) == GAD_ERR_SHAPE && says("65535"));
     EXPECT(gad_three_nn_grid_workspace_bytes(2, 0, 0) > 0);                                   // nothing to search is no error
+
+    // gad_backproject_depth(depth, depth_u16, depth_div, mask, A, B, H, W, xyz, count, pix, workspace, stream)
+    const uint8_t* nomask = nullptr;
+    auto bp = [&](const void* d, int u16, float div, const float* A, int B, int H, int W, float* xyz, int32_t* cnt, void* w) {
+        return gad_backproject_depth(d, u16, div, nomask, A, B, H, W, xyz, cnt, nullptr, w, nullptr);
+    };
+    EXPECT(bp(nullptr, 0, 1.f, p, 1, 8, 8, p, q, ws) == GAD_ERR_NULL && says("null pointer"));
+    EXPECT(bp(p, 0, 1.f, nullptr, 1, 8, 8, p, q, ws) == GAD_ERR_NULL && says("null pointer"));
+    EXPECT(bp(p, 0, 1.f, p, 1, 8, 8, nullptr, q, ws) == GAD_ERR_NULL && says("null pointer"));
+    EXPECT(bp(p, 0, 1.f, p, 1, 8, 8, p, nullptr, ws) == GAD_ERR_NULL && says("null pointer"));
+    EXPECT(bp(p, 0, 1.f, p, 1, 8, 8, p, q, nullptr) == GAD_ERR_NULL && says("workspace"));
+    EXPECT(bp(p, 0, 1.f, p, 1, 8, 8, p, q, odd) == GAD_ERR_SHAPE && says("aligned"));
+    EXPECT(bp(reinterpret_cast<void*>(0x1002), 0, 1.f, p, 1, 8, 8, p, q, ws) == GAD_ERR_SHAPE && says("element size"));
+    EXPECT(bp(reinterpret_cast<void*>(0x1001), 1, 5000.f, p, 1, 8, 8, p, q, ws) == GAD_ERR_SHAPE && says("element size"));
+    EXPECT(bp(p, 1, 0.f, p, 1, 8, 8, p, q, ws) == GAD_ERR_SHAPE && says("divisor"));
+    EXPECT(bp(p, 1, -5000.f, p, 1, 8, 8, p, q, ws) == GAD_ERR_SHAPE && says("divisor"));
+    EXPECT(bp(p, 3, 1.f, p, 1, 8, 8, p, q, ws) == GAD_ERR_SHAPE && says("depth_u16=3"));
+    EXPECT(bp(p, 0, 1.f, p, 1, 0, 8, p, q, ws) == GAD_ERR_SHAPE && says("outside 1..4096"));
+    EXPECT(bp(p, 0, 1.f, p, 1, 8, 4097, p, q, ws) == GAD_ERR_SHAPE && says("outside 1..4096"));
+    EXPECT(bp(p, 0, 1.f, p, -2, 8, 8, p, q, ws) == GAD_ERR_SHAPE && says("B=-2"));
+    EXPECT(bp(p, 0, 1.f, p, 128, 4096, 4096, p, q, ws) == GAD_ERR_SHAPE && says("beyond 2^31"));
+    EXPECT(bp(p, 0, 1.f, p, 2147483647, 1, 1, p, q, ws) == GAD_ERR_SHAPE && says("overflows"));
+    EXPECT(bp(nullptr, 0, 1.f, nullptr, 0, 8, 8, nullptr, nullptr, nullptr) == GAD_OK);       // no image: no launch
+    EXPECT(gad_backproject_depth_workspace_bytes(1, 112, 112) >= 13 * 4);
+    EXPECT(gad_backproject_depth_workspace_bytes(127, 4096, 4096) >= 127ll * 16384 * 4);
+    EXPECT(gad_backproject_depth_workspace_bytes(0, 8, 8) == 0);
+    EXPECT(gad_backproject_depth_workspace_bytes(128, 4096, 4096) == GAD_ERR_SHAPE && says("beyond 2^31"));
+    EXPECT(gad_backproject_depth_workspace_bytes(1, 4097, 8) == GAD_ERR_SHAPE && says("outside 1..4096"));
+    EXPECT(gad_backproject_depth_workspace_bytes(1, 8, -1) == GAD_ERR_SHAPE && says("outside 1..4096"));
+
+    // gad_cloud_gather_affine(src, src_stride, sel, A, B, n, dst, dst_stride, stream)
+    EXPECT(gad_cloud_gather_affine(nullptr, 0, nullptr, nullptr, 1, 4, p, 0, nullptr) == GAD_ERR_NULL && says("(src)"));
+    EXPECT(gad_cloud_gather_affine(p, 0, nullptr, nullptr, 1, 4, nullptr, 0, nullptr) == GAD_ERR_NULL && says("(dst)"));
+    EXPECT(gad_cloud_gather_affine(p, -1, nullptr, nullptr, 1, 4, p, 0, nullptr) == GAD_ERR_SHAPE && says("src_stride=-1"));
+    EXPECT(gad_cloud_gather_affine(p, 0, nullptr, nullptr, 1, 4, p, -1, nullptr) == GAD_ERR_SHAPE && says("dst_stride=-1"));
+    EXPECT(gad_cloud_gather_affine(p, 0, nullptr, nullptr, -1, 4, p, 0, nullptr) == GAD_ERR_SHAPE && says("B=-1"));
+    EXPECT(gad_cloud_gather_affine(p, 0, nullptr, nullptr, 1 << 16, 1 << 15, p, 0, nullptr) == GAD_ERR_SHAPE && says("beyond 2^31"));
+    EXPECT(gad_cloud_gather_affine(nullptr, 0, nullptr, nullptr, 3, 0, nullptr, 0, nullptr) == GAD_OK);       // no point: no launch
+
+    // gad_point_state_pack(src, src_stride, sel, A, lead, n_lead, lead_flag, B, n, state, stream)
+    EXPECT(gad_point_state_pack(nullptr, 0, nullptr, nullptr, p, 6, 1.f, 1, 4, p, nullptr) == GAD_ERR_NULL && says("(src)"));
+    EXPECT(gad_point_state_pack(p, 0, nullptr, nullptr, nullptr, 6, 1.f, 1, 4, p, nullptr) == GAD_ERR_NULL && says("(lead)"));
+    EXPECT(gad_point_state_pack(p, 0, nullptr, nullptr, p, 6, 1.f, 1, 4, nullptr, nullptr) == GAD_ERR_NULL && says("(state)"));
+    EXPECT(gad_point_state_pack(p, 0, nullptr, nullptr, p, -6, 1.f, 1, 4, p, nullptr) == GAD_ERR_SHAPE && says("n_lead=-6"));
+    EXPECT(gad_point_state_pack(p, 0, nullptr, nullptr, p, 2147483647, 1.f, 1, 2147483647, p, nullptr) == GAD_ERR_SHAPE && says("beyond 2^31"));
+    EXPECT(gad_point_state_pack(nullptr, 0, nullptr, nullptr, nullptr, 0, 1.f, 4, 0, nullptr, nullptr) == GAD_OK);   // no column: no launch
     if (g_failed) return 1;
     printf("ok\n");
     return 0;
