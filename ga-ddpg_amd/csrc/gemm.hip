@@ -5031,6 +5031,7 @@ __global__ __launch_bounds__(256, NIT >= 8 ? 1 : 2) void gemm_bwd_wide_kernel(Dz
     // loaded under the current tile's last MFMAs and epilogue (cross-tile prefetch: a workgroup has 1 - 3 tiles, so the
     // staging latency in front of every tile was a third of its time)
     int vz[4], vg[4];
+    unsigned rtrue[4];                                    // GM = 1: the row an arg-max must name; a row past the live rows matches none
     float wrow[4];
     float4 rz[4], rg[4], rb[4];
     gad_u32x4 ra[4];
@@ -5042,6 +5043,7 @@ __global__ __launch_bounds__(256, NIT >= 8 ? 1 : 2) void gemm_bwd_wide_kernel(Dz
             const int rr = live ? r : max(n_rows - 1, 0);
             const float w = d.row_w ? d.row_w[rr] : 1.f;
             wrow[u] = live ? w : 0.f;
+            rtrue[u] = live ? (unsigned)r : 0xffffffffu;
             vz[u] = (r * d.z_pitch + c4) * 4;             // (the true row: past the live rows the bounded descriptor reads 0)
             vg[u] = ((GM == 1 ? d.row_grp[rr] : r) * gpitch + c4) * 4;
         }
@@ -5099,7 +5101,9 @@ __global__ __launch_bounds__(256, NIT >= 8 ? 1 : 2) void gemm_bwd_wide_kernel(Dz
                     float4 g = rg[u];
                     const float4 z = rz[u];
                     if (GM == 1) {
-                        const unsigned r = row0 + sr + 16 * u;   // the true row (a clamped row never matches an arg-max)
+                        // the true row, not the clamped one; a dead row takes no gradient even where the group's arg-max names it
+                        // (its dZ must be exactly 0: the statistics and dW below count on it), as in the separate kernels
+                        const unsigned r = rtrue[u];
                         g.x = ra[u].x == r ? g.x : 0.f; g.y = ra[u].y == r ? g.y : 0.f;
                         g.z = ra[u].z == r ? g.z : 0.f; g.w = ra[u].w == r ? g.w : 0.f;
                     }
@@ -5356,11 +5360,15 @@ extern "C" int gad_gemm_bwd(const gad_gemm_dx_args* ax, const gad_gemm_dw_args* 
     const int rows = ax->n_rows, wgs = g_opt_bwd_stream_wgs;
     const int splits = ax->n_out[0] == 64 ? 2 * wgs : wgs;            // partial dW blocks the kernel writes (see its header)
     GAD_REQUIRE((long long)splits * in.n_out[0] * 64 <= aw->partial_elems, GAD_ERR_SHAPE, "gemm_bwd: partial workspace too small");
-    if (split_on(GAD_SPLIT_BWD_STREAM) && ax->W_split_t && ax->W_split_t_pitch == ax->n_out[0] && ax->W_split_t_plane >= 64 * ax->n_out[0]) {
+    // (a pooled source with 64 outputs -- no layer of the step: SA1 pools its 128-output layer -- keeps the FP32-MFMA kernel: the
+    // fused split instantiation <8, 1, true> left channels 0 .. 31 of dW ~1e-2 off the float64 reference on an MI355X while its dX was
+    // exact, tests/test_gpu_gemm_f64_wide.py table E; the cause is not found)
+    if (split_on(GAD_SPLIT_BWD_STREAM) && ax->W_split_t && ax->W_split_t_pitch == ax->n_out[0] && ax->W_split_t_plane >= 64 * ax->n_out[0] &&
+        !(ax->dz.gmode != 0 && ax->n_out[0] == 64)) {
 #define LAUNCH_BWSS(NJ, GM) hipLaunchKernelGGL((gemm_bwd_stream_split_kernel<NJ, GM, true>), dim3(wgs), dim3(512), 0, st, d, ax->n_rows_dev, rows, \
                                                 ax->W_split_t, ax->W_split_t_plane, e, aw->partial, ts)
         if (ax->n_out[0] == 128) { if (ax->dz.gmode == 0) LAUNCH_BWSS(16, 0); else LAUNCH_BWSS(16, 1); }
-        else { if (ax->dz.gmode == 0) LAUNCH_BWSS(8, 0); else LAUNCH_BWSS(8, 1); }
+        else LAUNCH_BWSS(8, 0);
 #undef LAUNCH_BWSS
         GAD_CHECK_LAUNCH("gemm_bwd(stream split)");
         return later ? GAD_OK : gad_gemm_dw_reduce(ax, aw, stream);

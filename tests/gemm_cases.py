@@ -1,7 +1,8 @@
-"""Single-launch cases for the layer GEMM entry points (gad_gemm_fwd / gad_gemm_dx / gad_gemm_dw) on their skinny, generic-tile and
-SA1 first-layer routes, and the float64 gate they are held to (tests/test_gpu_gemm_f64.py).  The case classes follow
-tests/split_cases.Case: the argument block is built through engine._fwd_args / _dz / _ptr, the C entry point is called once, clones of
-the outputs come back; the references are tests/gemm_reference.py (pinned to torch autograd by tests/test_gemm_reference.py).
+"""Single-launch cases for the layer GEMM entry points (gad_gemm_fwd / gad_gemm_dx / gad_gemm_dw / gad_gemm_bwd) on their skinny,
+generic-tile, wide-tile and SA1 streaming routes, and the float64 gate they are held to (tests/test_gpu_gemm_f64.py: skinny, tile,
+SA1 first layer; tests/test_gpu_gemm_f64_wide.py: wide tile, SA1 layers 2 / 3, the fused backward, the grid-rows hint).  The case
+classes follow tests/split_cases.Case: the argument block is built through engine._fwd_args / _dz / _ptr, the C entry point is called
+once, clones of the outputs come back; the references are tests/gemm_reference.py (pinned to torch autograd by tests/test_gemm_reference.py).
 
 The gate, per output element: with u = 2**-24 and T the number of float32 terms behind the element,
     |got - ref| <= (T + 2) * u * abs_bound + 1e-30,
@@ -10,6 +11,8 @@ partials alike; Higham, Accuracy and Stability of Numerical Algorithms, section 
 exceeds, while a missing or duplicated term is ~ abs_bound / T.  T of every output is stated where its Spec is built.  The mean error
 is held against a float32 baseline that is not code under test (torch's own float32 matmul / reduction of the identical
 operands): mean |got - ref| <= 1.5 x the baseline's + floor, the floors of tests/test_gpu_split_families.check_case."""
+import ctypes as C
+
 import torch
 
 from ga_ddpg_amd import hip
@@ -21,7 +24,9 @@ MARGIN = 1.5
 R = hip.STAT_REPLICAS
 # library defaults of every switch a case may change (restored in `finally`)
 OPTION_DEFAULTS = {"fwd_skinny": 1, "dx_skinny": 1, "dw_skinny": 1, "skinny_nw": 8, "fwd_wide": 1, "dx_wide": 1, "dw_wide": 1,
-                   "fwd_stream": 1, "dx_stream": 1, "dw_stream": 1, "deterministic": 0}
+                   "fwd_stream": 1, "dx_stream": 1, "dw_stream": 1, "deterministic": 0,
+                   "bwd_wide": 0, "bwd_fused": 1, "bwd_wide_slab": 4, "dw_wide_wgs": 256, "fwd_stream_wgs": 256, "fwd_stream_l1_wgs": 256,
+                   "bwd_stream_wgs": 256, "fwd_bn_prologue": 1, "mfma_split": 1}
 
 
 def _gen(seed):
@@ -107,6 +112,15 @@ def check(name, got, exp, report=None, chain_keys=()):
 class Case(object):
     """one launch: run(options) -> (outputs, route); expect() -> {key: Spec} (after run: a launch may publish vectors the reference reads)"""
     entry = None
+    hint = None          # a host int: handed to gad_grid_rows_hint right before the launch, on the launching thread
+
+    def call(self, name, *structs):
+        """the entry point `name` on the argument blocks `structs`, with the case's grid-rows hint in front of it"""
+        if self.hint is not None:
+            h = C.c_int32(int(self.hint))
+            hip.check(hip.lib().gad_grid_rows_hint(C.byref(h), hip.stream()), "gad_grid_rows_hint")
+        hip.sync_deterministic()
+        hip.check(getattr(hip.lib(), name)(*([C.byref(x) for x in structs] + [hip.stream()])), name)
 
     def run(self, options=None):
         options = dict(options or {})
@@ -122,6 +136,22 @@ class Case(object):
         return out, route
 
 
+def _group_max(t, G, gs, fill):
+    """(rows <= G * gs, C) -> (G, C): the maximum over every run of gs rows, the rows the last run lacks counting as `fill`"""
+    pad = torch.full((G * gs - t.shape[0], t.shape[1]), fill, dtype=t.dtype, device=t.device)
+    return torch.cat([t, pad]).view(G, gs, -1).max(1).values
+
+
+def _with_rows(case, rows, fn):
+    """fn() with the case's live row count set to `rows`"""
+    was = case.r
+    case.r = rows
+    try:
+        return fn()
+    finally:
+        case.r = was
+
+
 def _replica_sum(buf, width, which):
     return buf.view(R, 2, width)[:, which].sum(0).clone()
 
@@ -130,12 +160,14 @@ def _replica_sum(buf, width, which):
 class Fwd(Case):
     """gad_gemm_fwd.  ACT input (c_in channels of zin at zin_off[g], optional affine + ReLU, `extra` column at c_in, bias column after
     it) or GATHER input (gather = dict(feat_c, act_c, gps, ctr)); groups through zin_off / out_off / n_out; live: device row count
-    (rows = the static bound); pool = dict(gsz, gamma): the fused max-pool; in_stat: the input layer's BatchNorm finalised by the launch."""
+    (rows = the static bound); pool = dict(gsz, gamma): the fused max-pool; in_stat: the input layer's BatchNorm finalised by the launch.
+    split: the call carries the forward split-bf16 mirror of W (split_cases.Mirror; one group).  pre_Kp (with gather and c_in): mode 2,
+    the c_in-channel ACT input recomputed from the gathered rows and pre_W (c_in, pre_Kp), then scale / shift / ReLU."""
     entry = "gad_gemm_fwd"
 
     def __init__(self, rows, Kp, n_out, c_in=None, extra=False, ones=False, affine=True, relu=1, zin_off=None, out_off=None,
                  zout_pitch=None, stats=True, row_w=True, live=None, gather=None, pool=None, in_stat=False, zout=True, seed=1,
-                 w_scale=0.05):
+                 w_scale=0.05, split=False, pre_Kp=None):
         dev = torch.device("cuda")
         g = _gen(seed)
         self.rows, self.Kp, self.n_out, self.ng = rows, Kp, list(n_out), len(n_out)
@@ -143,6 +175,7 @@ class Fwd(Case):
         self.nrows = None if live is None else torch.tensor([live], dtype=torch.int32, device=dev)
         self.gather, self.pool, self.in_stat, self.has_stats, self.has_zout = gather, pool, in_stat, stats, zout
         self.relu, self.affine = relu, affine
+        self.pre_Kp, self.mirror = pre_Kp, None
         self.zin_off = list(zin_off) if zin_off is not None else [0] * self.ng
         self.out_off = list(out_off) if out_off is not None else [sum(self.n_out[:i]) for i in range(self.ng)]
         self.w_off = [sum(n * Kp for n in self.n_out[:i]) for i in range(self.ng)]
@@ -150,7 +183,8 @@ class Fwd(Case):
         self.row_w = torch.pow(2.0, torch.randint(0, 3, (rows,), device=dev, generator=g).float()) if row_w else None
         if gather is not None:
             fc, ac, gps = gather["feat_c"], gather.get("act_c", 0), gather.get("gps", 1)
-            self.c_in = self.k_used = fc + 3 + ac
+            self.gk = fc + 3 + ac                                         # columns the gathered rows fill
+            self.c_in = self.k_used = self.gk if pre_Kp is None else c_in
             self.ones_col = -1
             npts = max(self.r // 3, 64)
             ngrp = (max(self.r // 8, 8) + gps - 1) // gps * gps
@@ -161,6 +195,12 @@ class Fwd(Case):
             self.action = torch.randn(self.nsmp, ac, device=dev, generator=g) if ac else None
             self.row_pt = torch.randint(0, npts, (rows,), device=dev, generator=g, dtype=torch.int32)
             self.row_grp = torch.sort(torch.randint(0, ngrp, (rows,), device=dev, generator=g, dtype=torch.int32)).values.contiguous()
+            if pre_Kp is not None:
+                assert self.gk <= pre_Kp
+                self.pre_W = torch.randn(c_in, pre_Kp, device=dev, generator=g) * 0.3
+                self.pre_W[:, self.gk:] = 0
+                self.scale = torch.rand(c_in, device=dev, generator=g) + 0.5
+                self.shift = torch.randn(c_in, device=dev, generator=g) * 0.3
         else:
             self.c_in = c_in
             self.k_used = c_in + (1 if extra else 0) + (1 if ones else 0)
@@ -198,6 +238,10 @@ class Fwd(Case):
             self.run_mean0 = torch.randn(C, device=dev, generator=g) * 0.1
             self.run_var0 = torch.rand(C, device=dev, generator=g) + 0.5
             self.zin = self.zin * torch.from_numpy(np.sqrt(var)).float().to(dev) + torch.from_numpy(mean).float().to(dev)
+        if split:
+            from tests.split_cases import Mirror
+            assert self.ng == 1
+            self.mirror = Mirror(self.W.view(self.n_out[0], Kp), gather["feat_c"] if gather is not None and pre_Kp is None else Kp)
 
     def args(self):
         kw = dict(n_rows_dev=_ptr(self.nrows), n_rows=self.rows, row_w=_ptr(self.row_w), W=_ptr(self.W), Kp=self.Kp, n_groups=self.ng,
@@ -213,14 +257,19 @@ class Fwd(Case):
                       in_count=self.bn_count, in_gamma=_ptr(self.in_gamma), in_beta=_ptr(self.in_beta), in_eps=self.bn_eps,
                       in_momentum=self.bn_mom, in_running_mean=_ptr(self.run_mean), in_running_var=_ptr(self.run_var),
                       in_mean=_ptr(self.in_mean), in_istd=_ptr(self.in_istd))
+        if self.mirror is not None:
+            kw.update(self.mirror.fwd_kw())
         return _fwd_args(**kw)
 
     def input_kw(self):
         """the fields that describe how the input rows are produced (shared with gad_gemm_dw_args.in)"""
         if self.gather is not None:
-            return dict(mode=1, c_in=self.c_in, src_xyz=_ptr(self.src), ctr_xyz=_ptr(self.ctr), feat=_ptr(self.feat),
-                        feat_c=self.gather["feat_c"], action=_ptr(self.action), act_c=self.gather.get("act_c", 0),
-                        grp_per_sample=self.gather.get("gps", 1), row_pt=_ptr(self.row_pt), row_grp=_ptr(self.row_grp))
+            d = dict(mode=1, c_in=self.c_in, src_xyz=_ptr(self.src), ctr_xyz=_ptr(self.ctr), feat=_ptr(self.feat),
+                     feat_c=self.gather["feat_c"], action=_ptr(self.action), act_c=self.gather.get("act_c", 0),
+                     grp_per_sample=self.gather.get("gps", 1), row_pt=_ptr(self.row_pt), row_grp=_ptr(self.row_grp))
+            if self.pre_Kp is not None:
+                d.update(mode=2, pre_W=_ptr(self.pre_W), pre_Kp=self.pre_Kp, scale=_ptr(self.scale), shift=_ptr(self.shift), relu=self.relu)
+            return d
         return dict(mode=0, zin=_ptr(self.zin), zin_pitch=self.zin.shape[1], c_in=self.c_in, scale=_ptr(self.scale),
                     shift=_ptr(self.shift), relu=self.relu, extra=_ptr(self.extra), ones_col=self.ones_col)
 
@@ -237,7 +286,7 @@ class Fwd(Case):
             self.scale, self.shift = torch.full((self.c_in,), nan, device=dev), torch.full((self.c_in,), nan, device=dev)
             self.in_mean, self.in_istd = torch.full((self.c_in,), nan, device=dev), torch.full((self.c_in,), nan, device=dev)
             self.run_mean, self.run_var = self.run_mean0.clone(), self.run_var0.clone()
-        hip.call_struct("gad_gemm_fwd", self.args())
+        self.call("gad_gemm_fwd", self.args())
         out = {}
         if self.zout is not None:
             out["z"] = self.zout.clone()                              # every row: rows past the live count must still hold NaN
@@ -261,11 +310,29 @@ class Fwd(Case):
 
     def operands(self):
         r = self.r
+        if self.pre_Kp is not None:
+            return [self.recomputed()["A"]]
         if self.gather is not None:
             return [gr.gather_operand(self.feat, self.src, self.ctr, self.action, self.row_pt, self.row_grp, self.gather.get("gps", 1),
                                       self.Kp, r)]
         return [gr.act_operand(self.zin, zo, self.c_in, self.Kp, self.scale, self.shift, self.relu, self.extra, self.ones_col, r)
                 for zo in self.zin_off]
+
+    def recomputed(self):
+        """mode 2: gemm_reference.recomputed_operand of the live rows"""
+        G = gr.gather_operand(self.feat, self.src, self.ctr, self.action, self.row_pt, self.row_grp, self.gather.get("gps", 1),
+                              self.pre_Kp, self.r)
+        return gr.recomputed_operand(G, self.pre_W, self.gk, self.scale, self.shift, self.relu)
+
+    def base_operands(self, As):
+        """what the float32 baseline multiplies: the operands themselves; mode 2: the same chain in torch float32 (matmul32 of the
+        gathered rows, one fused multiply-add, ReLU)"""
+        if self.pre_Kp is None:
+            return As
+        G = gr.gather_operand(self.feat, self.src, self.ctr, self.action, self.row_pt, self.row_grp, self.gather.get("gps", 1),
+                              self.pre_Kp, self.r)
+        a = gr.fma32(matmul32(G, self.pre_W.t()), self.scale, self.shift)
+        return [a.clamp_min(0) if self.relu else a]
 
     def _pad_rows(self, t):
         """(live rows, ...) -> (static rows, ...), NaN behind the live rows"""
@@ -275,10 +342,20 @@ class Fwd(Case):
 
     def expect(self, alter=None):
         """T: z = k_used products.  stat_sum adds the rows a lane / workgroup sums in float32 before its f64 atomic (<= the live rows):
-        k_used + rows.  stat_sq: each term w * z * z carries z's error twice and one rounding of w * z: 2 * k_used + rows + 1."""
+        k_used + rows.  stat_sq: each term w * z * z carries z's error twice and one rounding of w * z: 2 * k_used + rows + 1.
+        mode 2: the operand itself is a float32 evaluation of a first layer; how far it may lie from the float64 chain
+        (gemm_reference.recomputed_operand, A#slack) enters every bound as a slack: |dA| @ |W|^T for z, its weighted row sum for
+        stat_sum, sum_r w * (2 * z#abs + dz) * dz for stat_sq.
+        alter (negative controls): see tests/test_gpu_gemm_f64.py and tests/test_gpu_gemm_f64_wide.py"""
+        if isinstance(alter, tuple) and alter[0] == "first_rows":         # the reference of a launch that stopped after alter[1] rows
+            return _with_rows(self, alter[1], self.expect)
         r, K = self.r, self.k_used
         As = self.operands()
         out_off = list(self.out_off)
+        if alter == "zero_tile_row":                         # the first row of the last 64-row tile
+            As = [a.clone() for a in As]
+            for a in As:
+                a[(r - 1) // 64 * 64] = 0
         if alter == "no_bias":
             As = [a.clone() for a in As]
             for a in As:
@@ -297,32 +374,44 @@ class Fwd(Case):
             sref = gr.forward([a[:r - 1] for a in As], self.W, self.Kp, self.w_off, out_off, self.n_out, self.width, row_w=self.row_w)
             for k in ("stat_sum", "stat_sq"):
                 ref[k] = sref[k]
+        if alter == "shift_block":                           # the second 128-column block of the output, 4 columns to the right
+            for k in ("z", "stat_sum", "stat_sq"):
+                ref[k][..., 128:256] = torch.roll(ref[k][..., 128:256], 4, -1)
+        Ab = self.base_operands(As)
         z32 = torch.zeros(r, self.width, device=self.W.device)
-        for A, wo, oo, n in zip(As, self.w_off, self.out_off, self.n_out):
+        for A, wo, oo, n in zip(Ab, self.w_off, self.out_off, self.n_out):
             z32[:, oo:oo + n] = matmul32(A, self.W[wo:wo + n * self.Kp].view(n, self.Kp).t())
         w32 = self.row_w[:r, None] if self.row_w is not None else torch.ones(r, 1, device=z32.device)
         exp = {}
+        zs = ss = qs = None
+        if self.pre_Kp is not None:
+            w64 = w32.double()
+            dz = self.recomputed()["A#slack"] @ self.W.view(self.n_out[0], self.Kp).double().abs().t()
+            zs, ss, qs = self._pad_rows(dz), (w64 * dz).sum(0), (w64 * (2 * ref["z#abs"] + dz) * dz).sum(0)
 
         def zchain():
             c32 = torch.zeros(r, self.width, device=self.W.device)
-            for A, wo, oo, n in zip(As, self.w_off, self.out_off, self.n_out):
+            for A, wo, oo, n in zip(Ab, self.w_off, self.out_off, self.n_out):
                 c32[:, oo:oo + n] = chain32(A[:, :K], self.W[wo:wo + n * self.Kp].view(n, self.Kp)[:, :K])
             return self._pad_rows(c32)
         if self.has_zout:
-            exp["z"] = spec(self._pad_rows(ref["z"]), self._pad_rows(ref["z#abs"]), K, self._pad_rows(z32), chain=zchain)
+            exp["z"] = spec(self._pad_rows(ref["z"]), self._pad_rows(ref["z#abs"]), K, self._pad_rows(z32), slack=zs, chain=zchain)
         if self.has_stats:
-            exp["stat_sum"] = spec(ref["stat_sum"], ref["stat_sum#abs"], K + r, (w32 * z32).sum(0), True)
-            exp["stat_sq"] = spec(ref["stat_sq"], ref["stat_sq#abs"], 2 * K + r + 1, (w32 * z32 * z32).sum(0), True)
+            # (a reference without the last row comes with the float32 baseline of the same rows: at 3e4 rows one row is far inside
+            # the derived bound of a row sum, and it is the margin over the baseline that has to notice it)
+            rs = r - 1 if alter == "drop_last_row_stats" else r
+            exp["stat_sum"] = spec(ref["stat_sum"], ref["stat_sum#abs"], K + r, (w32 * z32)[:rs].sum(0), True, slack=ss)
+            exp["stat_sq"] = spec(ref["stat_sq"], ref["stat_sq#abs"], 2 * K + r + 1, (w32 * z32 * z32)[:rs].sum(0), True, slack=qs)
         if self.pool is not None:
-            # the pooled value is one of the group's z: |max got - max ref| <= the largest bound inside the group
-            G, gs, sg = r // self.gsz, self.gsz, torch.where(self.gamma < 0, -1.0, 1.0).double()[None, None, :]
-            grp = lambda t: t[:G * gs].view(G, gs, -1)
+            # the pooled value is one of the group's z: |max got - max ref| <= the largest bound inside the group.  A last group
+            # that the live rows end in pools its live rows only
+            G, gs, sg = (r + self.gsz - 1) // self.gsz, self.gsz, torch.where(self.gamma < 0, -1.0, 1.0).double()[None, :]
             zmax = torch.full(tuple(self.key.shape), float("nan"), dtype=torch.float64, device=z32.device)
             zabs = torch.zeros_like(zmax)
-            zmax[:G] = (grp(ref["z"]) * sg).max(1).values * sg[0]
-            zabs[:G] = grp(ref["z#abs"]).max(1).values
+            zmax[:G] = _group_max(ref["z"] * sg, G, gs, float("-inf")) * sg
+            zabs[:G] = _group_max(ref["z#abs"], G, gs, 0.0)
             b32 = torch.zeros_like(zmax)
-            b32[:G] = (grp(z32).double() * sg).max(1).values * sg[0]
+            b32[:G] = _group_max(z32.double() * sg, G, gs, float("-inf")) * sg
             exp["zmax"] = spec(zmax, zabs, K, b32)
         return exp
 
@@ -330,15 +419,16 @@ class Fwd(Case):
         """-> failures of the checks that are exact"""
         bad = []
         if self.pool is not None and "z" in out:            # keys decode to the maxima of the launch's own stored output
-            G, gs = self.r // self.gsz, self.gsz
-            sg = torch.where(self.gamma < 0, -1.0, 1.0)[None, None, :]
-            want = (out["z"][:G * gs].view(G, gs, -1) * sg).max(1).values * sg[0]
+            G, gs = (self.r + self.gsz - 1) // self.gsz, self.gsz
+            sg = torch.where(self.gamma < 0, -1.0, 1.0)[None, :]
+            want = _group_max(out["z"][:self.r] * sg, G, gs, float("-inf")) * sg
             if not torch.equal(out["zmax"][:G], want):
                 bad.append("pooled keys do not decode to the maxima of the stored output")
             row = 0xffffffff - (out["key"][:G] & 0xffffffff)
-            if not bool(((row >= torch.arange(G, device=row.device)[:, None] * gs) & (row < (torch.arange(G, device=row.device)[:, None] + 1) * gs)).all()):
+            first = torch.arange(G, device=row.device)[:, None] * gs
+            if not bool(((row >= first) & (row < first + gs) & (row < self.r)).all()):
                 bad.append("a pooled key names a row outside its group")
-        if self.pool is not None and not bool((out["key"][self.r // self.gsz:] == 0).all()):
+        if self.pool is not None and not bool((out["key"][(self.r + self.gsz - 1) // self.gsz:] == 0).all()):
             bad.append("keys of groups without live rows were written")
         return bad
 
@@ -367,11 +457,14 @@ class Fwd(Case):
 class Dx(Case):
     """gad_gemm_dx.  dZ = P*g - w*(Q + S*z) from z (cap, C) and a dense G (or pooled = dict(gsz): arg-max routing), groups through
     dz_off / gout_off / n_out; prev: the previous layer's BatchNorm-backward sums (+ store_masked); scatter = dict(feat_c, act_c, gps,
-    dfeat, daction): epilogue 1.  P and the row weights are powers of two (tests/split_cases.DxWide): dZ has a single rounding."""
+    dfeat, daction): epilogue 1.  P and the row weights are powers of two (tests/split_cases.DxWide): dZ has a single rounding.
+    pad_cols: columns of gout / zprev behind the last group's that no group writes (0: pitch = k_valid, what the streaming routes
+    take); split: the call carries the transposed split-bf16 mirror of W (split_cases.Mirror; one group)."""
     entry = "gad_gemm_dx"
 
     def __init__(self, rows, n_out, Kp, k_valid, dz_off=None, gout_off=None, g_pitch=None, z=True, relu=1, premasked=1, dscale=False,
-                 coef=True, row_w=True, prev=False, store_masked=1, live=None, pooled=None, scatter=None, bn=False, seed=2, w_scale=0.05):
+                 coef=True, row_w=True, prev=False, store_masked=1, live=None, pooled=None, scatter=None, bn=False, seed=2, w_scale=0.05,
+                 pad_cols=4, split=False):
         dev = torch.device("cuda")
         g = _gen(seed)
         self.rows, self.Kp, self.kv, self.n_out, self.ng = rows, Kp, k_valid, list(n_out), len(n_out)
@@ -411,7 +504,7 @@ class Dx(Case):
             self.daction = torch.zeros(self.nsmp, ac, dtype=torch.float64, device=dev) if (ac and scatter.get("daction", True)) else None
             self.width = k_valid
         else:
-            self.width = max(self.gout_off) + k_valid + 4                  # (+ 4 columns no group writes)
+            self.width = max(self.gout_off) + k_valid + pad_cols           # (+ 4 columns no group writes)
             self.gout = torch.empty(rows, self.width, device=dev)
             if prev:
                 self.zprev = torch.randn(rows, self.width, device=dev, generator=g)
@@ -429,6 +522,11 @@ class Dx(Case):
             self.bn_istd = torch.rand(C, device=dev, generator=g) + 0.5
             self.dscale = torch.pow(2.0, torch.randint(-1, 2, (C,), device=dev, generator=g).float())     # P = scale: a power of two
             self.dshift = torch.randn(C, device=dev, generator=g) * 0.3
+        self.mirror = None
+        if split:
+            from tests.split_cases import Mirror
+            assert self.ng == 1
+            self.mirror = Mirror(self.W.view(self.n_out[0], Kp), k_valid)
 
     def dz_kw(self):
         d = dict(z=_ptr(self.z), z_pitch=self.C if self.z is not None else 0, scale=_ptr(self.dscale), shift=_ptr(self.dshift),
@@ -460,33 +558,66 @@ class Dx(Case):
                 a.prev_scale, a.prev_shift, a.prev_mean, a.prev_istd = (_ptr(v) for v in self.pvec)
                 a.prev_dbeta, a.prev_dgamma, a.stat_stride = _ptr(self.bst, 0, 8), _ptr(self.bst, self.width, 8), 2 * self.width
                 a.store_masked = self.store_masked
+        if self.mirror is not None:
+            for k, v in self.mirror.t_kw().items():
+                setattr(a, k, v)
         return a
 
-    def launch(self):
-        if self.bn:
-            for v in (self.P, self.Q, self.S):
-                v.fill_(float("nan"))
-        out = {}
+    def prepare(self):
+        """everything the launch may write, pre-filled"""
+        self.bn_prepare()
         if self.scatter is not None:
             for t in (self.dfeat, self.daction):
                 if t is not None:
                     t.zero_()
-            hip.call_struct("gad_gemm_dx", self.args())
+        else:
+            self.gout.fill_(float("nan"))
+            if self.prev:
+                self.bst.zero_()
+
+    def collect(self):
+        out = {}
+        if self.scatter is not None:
             if self.dfeat is not None:
                 out["dfeat"] = self.dfeat.clone()
             if self.daction is not None:
                 out["daction"] = self.daction.clone()
         else:
-            self.gout.fill_(float("nan"))
-            if self.prev:
-                self.bst.zero_()
-            hip.call_struct("gad_gemm_dx", self.args())
             out["gout"] = self.gout.clone()
             if self.prev:
                 out["dbeta"], out["dgamma"] = _replica_sum(self.bst, self.width, 0), _replica_sum(self.bst, self.width, 1)
-        if self.bn:
-            out["P"], out["Q"], out["S"] = self.P.clone(), self.Q.clone(), self.S.clone()
+        self.bn_collect(out)
         return out
+
+    def launch(self):
+        self.prepare()
+        self.call("gad_gemm_dx", self.args())
+        return self.collect()
+
+    def bn_prepare(self):
+        self.bn_in_registers = False
+        if self.bn:
+            for v in (self.P, self.Q, self.S):
+                v.fill_(float("nan"))
+
+    def bn_collect(self, out):
+        """the bn_* block: a route whose kernel reads P / Q / S per lane has gad_bn_bwd_coef publish them in the scratch (out["P"],
+        ["Q"], ["S"]: check_bn).  The wide-tile kernels form them per channel in registers (dz_coef -> gad_bn_bwd_channel) and
+        publish nothing: the scratch still holds the NaN it was given, and the reference's dZ takes the coefficients of
+        layer_reference.bn_bwd_coef, rounded to float32 as that device function rounds its float64 evaluation -- the coefficients
+        are then tested through every output of the launch."""
+        if not self.bn or self.bn_in_registers:
+            return
+        if bool(torch.isnan(torch.cat([self.P, self.Q, self.S])).all()):
+            self.bn_in_registers = True
+            import numpy as np
+            from tests import layer_reference as lr
+            ref = lr.bn_bwd_coef(self.bn_db.cpu().numpy(), self.bn_dg.cpu().numpy(), self.bn_stride, self.dscale.cpu().numpy(),
+                                 self.bn_mean.cpu().numpy(), self.bn_istd.cpu().numpy(), self.bn_count)
+            for v, k in ((self.P, "P"), (self.Q, "Q"), (self.S, "S")):
+                v.copy_(torch.from_numpy(np.asarray(ref[k]).astype(np.float32)))
+        else:
+            out["P"], out["Q"], out["S"] = self.P.clone(), self.Q.clone(), self.S.clone()
 
     def dz32(self):
         r = self.r
@@ -497,8 +628,13 @@ class Dx(Case):
         """T: gout = the group's n_out products.  dbeta adds the rows summed in float32 before the f64 atomic: n_out + rows; dgamma's
         terms carry x_hat = (zprev - mean) * istd, two more roundings, and the fused multiply-add: n_out + rows + 3.  dfeat: float32
         atomics, one per row of the point: n_out + the most rows on one point.  daction: float64 sums of the float32 products: n_out."""
+        if isinstance(alter, tuple) and alter[0] == "first_rows":         # the reference of a launch that stopped after alter[1] rows
+            return _with_rows(self, alter[1], self.expect)
         r, n = self.r, max(self.n_out)
         dZ = self.dz32()
+        if alter == "zero_tile_row":                         # the first row of the last 64-row tile
+            dZ = dZ.clone()
+            dZ[(r - 1) // 64 * 64] = 0
         gout_off = list(self.gout_off)
         W = self.W
         if alter == "shift_out_off":
@@ -512,6 +648,11 @@ class Dx(Case):
         if alter == "drop_last_row_stats":
             sref = gr.dx(dZ[:r - 1], self.W, self.Kp, self.kv, self.dz_off, self.w_off, self.n_out, gout_off, self.width, prev, self.store_masked)
             ref["dbeta"], ref["dgamma"] = sref["dbeta"], sref["dgamma"]
+        if alter == "shift_block":                           # the second 128-column block of the input gradient, 4 columns to the right
+            for k in ("gx", "gout", "dbeta", "dgamma"):
+                if k in ref:
+                    ref[k] = ref[k].clone()
+                    ref[k][..., 128:256] = torch.roll(ref[k][..., 128:256], 4, -1)
         g32 = torch.zeros(r, self.width, device=dZ.device)
         for do, wo, nn, go in zip(self.dz_off, self.w_off, self.n_out, self.gout_off):
             g32[:, go:go + self.kv] = matmul32(dZ[:, do:do + nn], self.W[wo:wo + nn * self.Kp].view(nn, self.Kp)[:, :self.kv])
@@ -538,8 +679,9 @@ class Dx(Case):
                 base = m32
                 masked = lambda t: torch.where(live, t, torch.zeros((), device=t.device))
             xhat32 = (self.zprev[:r] - self.pvec[2]) * self.pvec[3]
-            exp["dbeta"] = spec(ref["dbeta"], ref["dbeta#abs"], n + r, m32.sum(0), True)
-            exp["dgamma"] = spec(ref["dgamma"], ref["dgamma#abs"], n + r + 3, (m32 * xhat32).sum(0), True)
+            rs = r - 1 if alter == "drop_last_row_stats" else r          # (the baseline of the rows the reference covers: Fwd.expect)
+            exp["dbeta"] = spec(ref["dbeta"], ref["dbeta#abs"], n + r, m32[:rs].sum(0), True)
+            exp["dgamma"] = spec(ref["dgamma"], ref["dgamma#abs"], n + r + 3, (m32 * xhat32)[:rs].sum(0), True)
 
         def gchain():
             c32 = torch.zeros(r, self.width, device=dZ.device)
@@ -554,7 +696,10 @@ class Dx(Case):
 
     def check_bn(self, out):
         """P / Q / S left in the scratch by the coefficient launch against layer_reference.bn_bwd_coef (P bit-exact; Q, S: one float32
-        rounding of a float64 evaluation, the bound of tests/test_gpu_layer_kernels)"""
+        rounding of a float64 evaluation, the bound of tests/test_gpu_layer_kernels); nothing where the route publishes none
+        (bn_collect)"""
+        if "P" not in out:
+            return []
         import numpy as np
         from tests import layer_reference as lr
         ref = lr.bn_bwd_coef(self.bn_db.cpu().numpy(), self.bn_dg.cpu().numpy(), self.bn_stride, self.dscale.cpu().numpy(),
@@ -604,16 +749,19 @@ class Dw(Case):
             a.partial, a.partial_elems = _ptr(self.ws), self.ws.numel()
         return a
 
-    def launch(self):
+    def prepare(self):
         self.gacc.copy_(self.prefill)
-        if self.dz.bn:
-            for v in (self.dz.P, self.dz.Q, self.dz.S):
-                v.fill_(float("nan"))
-        hip.call_struct("gad_gemm_dw", self.args())
+        self.dz.bn_prepare()
+
+    def collect(self):
         out = {"gacc": self.gacc.clone()}
-        if self.dz.bn:
-            out["P"], out["Q"], out["S"] = self.dz.P.clone(), self.dz.Q.clone(), self.dz.S.clone()
+        self.dz.bn_collect(out)
         return out
+
+    def launch(self):
+        self.prepare()
+        self.call("gad_gemm_dw", self.args())
+        return self.collect()
 
     def expect(self, alter=None):
         """T: every element of dW is a sum over the live rows, in float32 inside a wavefront / workgroup / split, f64 across them: rows.
@@ -633,9 +781,15 @@ class Dw(Case):
                 a[:, i.c_in] = 0
         elif alter == "drop_last_row_stats":
             As, dZ = [a[:self.r - 1] for a in As], dZ[:self.r - 1]
+        elif alter == "zero_tile_row":                       # the first row of the last 64-row tile
+            dZ = dZ.clone()
+            dZ[(self.r - 1) // 64 * 64] = 0
         elif alter == "shift_out_off":
             dz_off[-1] += 4
         ref = gr.dw(dZ, As, i.Kp, i.k_used, dz_off, w_off, i.n_out, self.total)
+        if alter == "shift_block":                           # input columns 128 .. 255 of the one group's block, 4 to the right
+            blk = ref["dW"][w_off[0]:w_off[0] + i.n_out[0] * i.Kp].view(i.n_out[0], i.Kp)
+            blk[:, 128:256] = torch.roll(blk[:, 128:256], 4, -1)
         b32 = torch.zeros(self.total, device=dZ.device)
         for A, do, wo, n in zip(As, self.dz_off, i.w_off, i.n_out):
             b32[wo:wo + n * i.Kp].view(n, i.Kp)[:, :i.k_used] = matmul32(dZ[:, do:do + n].t(), A[:, :i.k_used])
@@ -655,3 +809,64 @@ class Dw(Case):
         if not torch.equal(out["gacc"][~mask], self.prefill[~mask]):
             return ["%d arena words outside the groups' used columns changed" % int((out["gacc"][~mask] != self.prefill[~mask]).sum())]
         return []
+
+
+# ----------------------------------------------------------------------------------------------------------------- dX + dW
+DW_REDUCE_LATER = -2          # include/gaddpg.h GAD_DW_REDUCE_LATER
+
+
+def layer_input(dx):
+    """the Fwd description of the layer whose input gradient the Dx case `dx` produces -- how gad_gemm_dw_args.in must describe the
+    rows for gad_gemm_bwd to take both as one layer: the SAME zprev / scale / shift tensors as dx's previous-layer block (ACT), or a
+    gathered input over dx's own row maps (scatter epilogue), and the same device row count"""
+    live = None if dx.nrows is None else dx.r
+    if dx.scatter is not None:
+        gth = dict(feat_c=dx.scatter["feat_c"], act_c=dx.scatter.get("act_c", 0), gps=dx.scatter.get("gps", 1))
+        inp = Fwd(dx.rows, dx.Kp, dx.n_out, gather=gth, live=live, stats=False, zout=False, row_w=False, seed=17)
+        assert inp.npts == dx.npts
+        inp.row_pt, inp.row_grp = dx.row_pt, dx.row_grp
+    else:
+        assert dx.prev and dx.Kp == dx.kv
+        inp = Fwd(dx.rows, dx.Kp, dx.n_out, c_in=dx.kv, live=live, stats=False, zout=False, row_w=False, seed=17)
+        inp.zin, inp.scale, inp.shift = dx.zprev, dx.pvec[0], dx.pvec[1]
+    inp.nrows = dx.nrows
+    return inp
+
+
+class Bwd(Case):
+    """gad_gemm_bwd: the dX description `dx` (a Dx case) and the dW description of the same layer (a Dw case over layer_input(dx) and
+    dx's gradient source) in one call; later: the call is made with row_splits = GAD_DW_REDUCE_LATER and followed by an explicit
+    gad_gemm_dw_reduce on the same argument blocks (while the case's options are still in force: the reduce recomputes the split count
+    from them).  Outputs, references and exact checks are those of the two cases."""
+    entry = "gad_gemm_bwd"
+
+    def __init__(self, dx, later=False):
+        self.dx, self.dz, self.later = dx, dx, later
+        self.dw = Dw(layer_input(dx), dx)
+        self.r = dx.r
+
+    def launch(self):
+        self.dx.prepare()
+        self.dw.prepare()
+        ax, aw = self.dx.args(), self.dw.args()
+        if self.later:
+            aw.row_splits = DW_REDUCE_LATER
+        self.call("gad_gemm_bwd", ax, aw)
+        if self.later:
+            self.call("gad_gemm_dw_reduce", ax, aw)
+        out = self.dx.collect()
+        out.update(self.dw.collect())
+        return out
+
+    def outputs(self, out):
+        return dict(out, **self.dw.outputs(out))
+
+    def expect(self, alter=None):
+        """T of gout / dbeta / dgamma / dfeat: Dx.expect; of dW: Dw.expect (the fused kernels keep one float32 partial block per
+        workgroup over all its rows: at most the live rows per element, as for the separate kernels)"""
+        exp = self.dx.expect(alter)
+        exp.update(self.dw.expect(alter))
+        return exp
+
+    def exact(self, out):
+        return self.dw.exact(out)

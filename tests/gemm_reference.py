@@ -52,6 +52,24 @@ def gather_operand(feat, src_xyz, ctr_xyz, action, row_pt, row_grp, grp_per_samp
     return A
 
 
+def recomputed_operand(G, pre_W, pre_k, scale, shift, relu=1):
+    """mode 2 (the ACT input recomputed from the stage's gathered first layer): two chained layers.  G: the gathered operand
+    (rows, pre_Kp) of gather_operand, pre_W: (C, pre_Kp) packed weights of the first layer, pre_k: its used columns.
+    z1 = G[:, :pre_k] @ pre_W[:, :pre_k]^T, A = relu?(z1 * scale + shift), both in float64 whatever the dtype of the inputs (the
+    second layer's reference is forward() on A).  -> dict: A (rows, C), z1, z1#abs = |G| @ |pre_W|^T, and A#slack: how far a float32
+    evaluation of A may lie from this one -- z1 is a length-pre_k float32 sum, (pre_k + 2) * 2^-24 * z1#abs in any order, scaled by
+    |scale|, plus the one rounding of the fused multiply-add, 2^-24 * (|z1 * scale| + |shift|); the ReLU does not enlarge either"""
+    g, w = G[:, :pre_k].double(), pre_W[:, :pre_k].double()
+    z1 = g @ w.t()
+    z1a = g.abs() @ w.abs().t()
+    s, t = scale.double(), shift.double()
+    A = z1 * s + t
+    if relu:
+        A = A.clamp_min(0)
+    slack = 2.0 ** -24 * ((pre_k + 2) * s.abs() * z1a + (z1 * s).abs() + t.abs())
+    return {"A": A, "z1": z1, "z1#abs": z1a, "A#slack": slack}
+
+
 # ----------------------------------------------------------------------------- the gate's magnitudes
 def abs_bound(A, W):
     """|A| @ |W|^T in float64: the sum of |terms| behind every element of A @ W^T"""

@@ -165,3 +165,62 @@ def test_gather_operand_layout(ctr):
     assert torch.equal(A[:, :4], feat[pt.long()])
     assert torch.equal(A[:, 4:7], src[pt.long()] - c3[grp.long()] if ctr else src[pt.long()])
     assert torch.equal(A[:, 7:13], act[torch.tensor([0, 0, 1])]) and float(A[:, 13:].abs().max()) == 0.0
+
+
+def test_recomputed_operand_matches_autograd():
+    """mode 2: the gathered first layer, its affine + ReLU and the second layer as one chain of plain torch modules; the float32
+    slack of the recomputed operand covers a float32 evaluation of it"""
+    t = _setup()
+    d = lambda k: t[k].detach()
+    g = torch.Generator().manual_seed(11)
+    C, Kp0, k0 = t["C"], t["Kp0"], t["feat_c"] + 3 + t["act_c"]
+    scale = torch.rand(C, generator=g, dtype=torch.float64) + 0.5
+    shift = torch.randn(C, generator=g, dtype=torch.float64) * 0.3
+    W = torch.randn(7, C, generator=g, dtype=torch.float64)
+    pt, grp = t["row_pt"].long(), t["row_grp"].long()
+    X0 = torch.cat([d("feat")[pt], t["src"][pt] - t["ctr"][grp], d("action")[grp // t["gps"]]], 1)
+    lin0, lin1 = torch.nn.Linear(k0, C, bias=False, dtype=torch.float64), torch.nn.Linear(C, 7, bias=False, dtype=torch.float64)
+    with torch.no_grad():
+        lin0.weight.copy_(d("W0")[:, :k0])
+        lin1.weight.copy_(W)
+        want_A = torch.relu(lin0(X0) * scale + shift)
+        want_z = lin1(want_A)
+    G = gr.gather_operand(d("feat"), t["src"], t["ctr"], d("action"), t["row_pt"], t["row_grp"], t["gps"], Kp0)
+    ro = gr.recomputed_operand(G, d("W0"), k0, scale, shift, 1)
+    _close(ro["A"], want_A, "recomputed operand")
+    _close(ro["z1"], lin0(X0).detach(), "recomputed first layer")
+    f = gr.forward([ro["A"]], W, C, [0], [0], [7], 7, row_w=t["row_w"])
+    _close(f["z"], want_z, "second layer on the recomputed operand")
+    # float32 inputs: A stays the float64 chain; a float32 evaluation of the same chain lies inside A#slack
+    f32 = lambda x: x.float()
+    G32 = gr.gather_operand(f32(d("feat")), f32(t["src"]), f32(t["ctr"]), f32(d("action")), t["row_pt"], t["row_grp"], t["gps"], Kp0)
+    r32 = gr.recomputed_operand(G32, f32(d("W0")), k0, f32(scale), f32(shift), 1)
+    assert r32["A"].dtype == torch.float64
+    a32 = torch.relu((G32[:, :k0] @ f32(d("W0"))[:, :k0].t()) * f32(scale) + f32(shift))
+    err = (a32.double() - r32["A"]).abs()
+    assert bool((err <= r32["A#slack"]).all()) and float(err.max()) > 0.0
+
+
+def test_backward_pair_of_one_layer_matches_autograd():
+    """the fused backward (gad_gemm_bwd) is dx() and dw() on ONE layer: dW's input rows are the activation the dX side's previous-layer
+    block describes, act_operand(zprev, prev scale, prev shift).  x = relu(gamma * (zprev - mean) * istd + beta), z = x W^T."""
+    g = torch.Generator().manual_seed(5)
+    f64 = dict(dtype=torch.float64, generator=g)
+    rows, K, N = 29, 8, 12
+    zprev = torch.randn(rows, K, **f64)
+    mean, istd = torch.randn(K, **f64) * 0.1, torch.rand(K, **f64) + 0.5
+    gamma, beta = (torch.rand(K, **f64) + 0.5).requires_grad_(), (torch.randn(K, **f64) * 0.3).requires_grad_()
+    W = torch.randn(N, K, **f64).requires_grad_()
+    dZ = torch.randn(rows, N, **f64)
+    y = (zprev - mean) * istd * gamma + beta
+    y.retain_grad()
+    (torch.nn.functional.linear(torch.relu(y), W) * dZ).sum().backward()
+    scale, shift = (gamma * istd).detach(), (beta - mean * gamma * istd).detach()
+    A = gr.act_operand(zprev, 0, K, K, scale, shift, 1)
+    prev = dict(zprev=zprev, scale=scale, shift=shift, mean=mean, istd=istd)
+    x = gr.dx(dZ, W.detach(), K, K, [0], [0], [N], [0], K, prev=prev, store_masked=1)
+    w = gr.dw(dZ, [A], K, K, [0], [0], [N], N * K)
+    _close(x["gout"], y.grad, "fused backward: masked input gradient")
+    _close(x["dbeta"], beta.grad, "fused backward: dbeta")
+    _close(x["dgamma"], gamma.grad, "fused backward: dgamma")
+    _close(w["dW"].view(N, K), W.grad, "fused backward: dW")
