@@ -18,570 +18,23 @@
 // before the first wait, instead of one s_waitcnt per predicated load.
 // BatchNorm statistics: registers -> __shfl_xor -> LDS across wavefronts -> f64 device atomics
 // into one of GAD_STAT_REPLICAS accumulators (blockIdx % replicas) to bound same-address contention.
-#include "common.hpp"
+//
+// Map of the family (a kernel template is defined and instantiated in exactly one unit):
+//   gemm_common.hpp  what the units share: operand producers, tile staging, MFMA tile, epilogue helpers, split-bf16 arithmetic,
+//                    diagnostic macros, GemmOptions, declarations of the host functions that cross the units
+//   gemm.hip         this file: the option block and gad_set_option, the deterministic mode's scratch and ordered reduce, the host
+//                    helpers the passes share (split_on, fits_i32_bytes, check_input, coef_fallback) -- and, until they get units
+//                    of their own (gemm_fwd / gemm_dx / gemm_bwd.hip), the forward, dX and fused backward kernels with
+//                    gad_gemm_fwd, gad_gemm_dx, gad_gemm_bwd and gad_gemm_dw_reduce
+//   gemm_dw.hip      gad_gemm_dw: tile, skinny, streaming, gather-streaming, wide and wide-split dW kernels; dw_reduce_kernel
+#include "gemm_common.hpp"
 #include <mutex>
-#include <type_traits>
 #include <string.h>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+GemmOptions g_opt;
 
-// cache policy of the streaming kernels' big output stores (buffer-store aux bits: 0 plain, 2 nt, 16 sc1 = write-through)
-#ifndef GAD_STREAM_STORE_AUX
-#define GAD_STREAM_STORE_AUX 0
-#endif
-
-#define KT 32   // reduction tile
-
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 f4sel(bool c, float4 a, float4 b) {
-    return make_float4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w);
-}
-__device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
-typedef unsigned gad_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 buf_ld4(__amdgpu_buffer_rsrc_t r, int vo, int so) {
-    const gad_u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(r, vo, so, 0);
-    return make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
-}
-__device__ __forceinline__ float buf_ld(__amdgpu_buffer_rsrc_t r, int vo, int so) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0));
-}
-// buffer descriptors address 32-bit UNSIGNED byte offsets: a row tensor may reach 2 GiB (the host-side route predicates bound
-// rows x pitch x 4 by 2^31 inclusive, fits_i32_bytes) -- record counts are formed in unsigned arithmetic
-#define GAD_BUF_MAX ((int)0x80000000u)
-__device__ __forceinline__ int gad_nbytes(int rows, int row_bytes) { return (int)((unsigned)rows * (unsigned)row_bytes); }
-
-
-// ------------------------------------------------------------------------------------------------
-// operand producers.  Every producer is split in two so that global loads overlap the MFMAs:
-//   *_raw    issues the 16-byte loads of the NEXT tile into registers (no arithmetic on them),
-//   *_finish runs after the current tile's MFMAs, right before the LDS store: BatchNorm affine /
-//            ReLU / BatchNorm-backward with the per-channel vectors read from LDS.
-// ------------------------------------------------------------------------------------------------
-#define VMAX 1024            // max channels of one layer side (per-channel vectors staged in LDS)
-
-struct XSrc {   // how a layer's INPUT row r, column c is produced (gad_gemm_fwd_args subset)
-    int mode;
-    const float* zin; int zin_pitch; int c_in;
-    const float* scale; const float* shift; int relu;
-    const float* extra; int ones_col;
-    const float* src_xyz; const float* ctr_xyz; const float* feat; int feat_c;
-    const float* action; int act_c; int gps;
-    const int32_t* row_pt; const int32_t* row_grp;
-    int affine;          // ACT input: a per-channel affine (scale / shift) is applied
-    const float* pre_W; int pre_Kp;   // mode 2: the ACT input is RECOMPUTED from the gathered first layer (its packed weights)
-    gad_bn_fin bn;       // input layer's BatchNorm finalised in this launch's prologue (bn.stat_sum == NULL: scale / shift as given)
-};
-
-static XSrc make_xsrc(const gad_gemm_fwd_args& a) {
-    XSrc x;
-    x.mode = a.mode; x.zin = a.zin; x.zin_pitch = a.zin_pitch; x.c_in = a.c_in;
-    x.scale = a.scale; x.shift = a.shift; x.relu = a.relu; x.extra = a.extra; x.ones_col = a.ones_col;
-    x.src_xyz = a.src_xyz; x.ctr_xyz = a.ctr_xyz; x.feat = a.feat; x.feat_c = a.feat_c;
-    x.action = a.action; x.act_c = a.act_c; x.gps = a.grp_per_sample > 0 ? a.grp_per_sample : 1;
-    x.row_pt = a.row_pt; x.row_grp = a.row_grp;
-    x.affine = (x.scale && x.shift) ? 1 : 0;
-    x.pre_W = a.pre_W; x.pre_Kp = a.pre_Kp;
-    x.bn.stat_sum = a.in_stat_sum; x.bn.stat_sq = a.in_stat_sq; x.bn.stat_stride = a.in_stat_stride; x.bn.count = a.in_count;
-    x.bn.gamma = a.in_gamma; x.bn.beta = a.in_beta; x.bn.eps = a.in_eps; x.bn.momentum = a.in_momentum;
-    x.bn.running_mean = a.in_running_mean; x.bn.running_var = a.in_running_var;
-    x.bn.scale = const_cast<float*>(a.scale); x.bn.shift = const_cast<float*>(a.shift); x.bn.mean = a.in_mean; x.bn.istd = a.in_istd;
-    return x;
-}
-
-// per-channel affine of an ACT input -> LDS
-template <int NT>
-__device__ __forceinline__ void stage_affine(float* sv, float* tv, const XSrc& x, int off, int n) {
-    for (int i = threadIdx.x; i < n; i += NT) { sv[i] = x.scale[off + i]; tv[i] = x.shift[off + i]; }
-}
-
-// diagnostic build (-DGAD_X_PHASES=1, tools/ubench_phases.py): the streaming forward kernel writes each wavefront's cycles per
-// phase (wait + prefetch | MFMA loop | epilogue) into the launch's timing slot instead of the start / end stamps
-#ifdef GAD_X_PHASES
-#define GAD_PH_STAMP(t) t = (long long)__builtin_readcyclecounter()
-#else
-#define GAD_PH_STAMP(t)
-#endif
-// diagnostic build (-DGAD_W_PHASES, tools/ubench_wphases.py): the wide-tile forward / dX kernels write, per workgroup, the wall
-// clock (100 MHz) at the end of each part of their first row tile -- prologue | first tile staged | K loop | stores + statistics |
-// column atomics -- into the upper half of the launch's timing slot (entries 8192 + workgroup)
-#ifdef GAD_W_PHASES
-#define GAD_WPH_DECL long long wph_[6] = {0, 0, 0, 0, 0, 0}; wph_[0] = (long long)wall_clock64()
-#define GAD_WPH(i) do { if (wph_[i] == 0) wph_[i] = (long long)wall_clock64(); } while (0)
-#define GAD_WPH_STORE(ts)                                                                                                     \
-    do {                                                                                                                      \
-        unsigned long long* q_ = reinterpret_cast<unsigned long long*>(reinterpret_cast<size_t>(ts) & ~(size_t)7);            \
-        const unsigned blk_ = blockIdx.x + gridDim.x * blockIdx.y;                                                            \
-        if (q_ && threadIdx.x == 0 && blk_ < 4096) {                                                                          \
-            auto c_ = [&](int i) { const long long d_ = wph_[i] ? wph_[i] - wph_[0] : 0; return (unsigned long long)(d_ > 65535 ? 65535 : d_); }; \
-            q_[2 * (8192 + blk_)] = (unsigned long long)wph_[0];                                                              \
-            q_[2 * (8192 + blk_) + 1] = c_(1) | (c_(2) << 16) | (c_(3) << 32) | (c_(4) << 48);                                \
-            q_[2 * (12288 + blk_)] = c_(5);                                                                                    \
-        }                                                                                                                     \
-    } while (0)
-// ... and, summed over the K-tiles of the first row tile, every wavefront's shader cycles in: fragments + MFMAs issued | next tile
-// staged + loads issued | barrier wait (entries 4096 + 8 * workgroup + wavefront: {mfma << 32 | stage, barrier})
-#define GAD_WKL_DECL long long wkl_[4] = {0, 0, 0, 0}; long long wkt_ = 0, wkp_ = 0
-#define GAD_WKL(i)                                                                   \
-    do {                                                                             \
-        wkt_ = (long long)__builtin_readcyclecounter();                              \
-        if (i > 0) wkl_[i] += wkt_ - wkp_;                                           \
-        wkp_ = wkt_;                                                                 \
-    } while (0)
-#define GAD_WKL_STORE(ts)                                                                                                     \
-    do {                                                                                                                      \
-        unsigned long long* q_ = reinterpret_cast<unsigned long long*>(reinterpret_cast<size_t>(ts) & ~(size_t)7);            \
-        const unsigned blk_ = blockIdx.x + gridDim.x * blockIdx.y;                                                            \
-        if (q_ && (threadIdx.x & 63) == 0 && blk_ < 512) {                                                                    \
-            const unsigned e_ = 4096 + 8 * blk_ + (threadIdx.x >> 6);                                                         \
-            q_[2 * e_] = ((unsigned long long)wkl_[1] << 32) | (unsigned long long)(wkl_[2] & 0xffffffffu);                   \
-            q_[2 * e_ + 1] = (unsigned long long)wkl_[3];                                                                     \
-        }                                                                                                                     \
-    } while (0)
-#else
-#define GAD_WPH_DECL
-#define GAD_WPH(i)
-#define GAD_WPH_STORE(ts)
-#define GAD_WKL_DECL
-#define GAD_WKL(i)
-#define GAD_WKL_STORE(ts)
-#endif
-struct XRaw { float4 a; float4 s; };     // a: the 16 raw bytes; s: special columns (tail tiles only)
-
-// number of leading "bulk" columns served by aligned 16-byte loads
-__device__ __forceinline__ int x_bulk(const XSrc& x) { return x.mode == 0 ? x.c_in : x.feat_c; }
-
-// ACT input: columns [0,c_in) = act(scale*z+shift) of the previous layer's raw output (c_in % 4 == 0),
-//            column c_in = extra[r] (optional), column ones_col = 1, everything else 0.
-// GATHER input (packed order, features first): [feat[pt] (feat_c) | src_xyz[pt]-ctr_xyz[grp] (3) |
-//            action[grp/gps] (act_c) | 0..].
-// `tail` (wave-uniform): this K-tile reaches beyond the bulk columns.  `pt`: point index of the row.
-template <int XM>
-__device__ __forceinline__ XRaw x_raw(const XSrc& x, int r, bool valid, int zoff, int c, bool tail, int pt, int grp_pre = -1) {
-    XRaw o;
-    o.s = f4zero();
-    const int rr = valid ? r : 0;
-    if (XM == 0) {
-        const int cc = c < x.c_in ? c : x.c_in - 4;
-        o.a = ldg4(x.zin + (size_t)rr * x.zin_pitch + zoff + cc);
-        if (tail) {
-            float e = 0.f;
-            if (x.extra) e = x.extra[rr];
-            o.s.x = (c + 0 == x.c_in && x.extra) ? e : (c + 0 == x.ones_col ? 1.f : 0.f);
-            o.s.y = (c + 1 == x.c_in && x.extra) ? e : (c + 1 == x.ones_col ? 1.f : 0.f);
-            o.s.z = (c + 2 == x.c_in && x.extra) ? e : (c + 2 == x.ones_col ? 1.f : 0.f);
-            o.s.w = (c + 3 == x.c_in && x.extra) ? e : (c + 3 == x.ones_col ? 1.f : 0.f);
-        }
-    } else {
-        const int cc = c < x.feat_c ? c : x.feat_c - 4;
-        o.a = ldg4(x.feat + (size_t)pt * x.feat_c + cc);
-        if (tail) {
-            const int grp = grp_pre >= 0 ? grp_pre : x.row_grp[rr];
-            const float* p = x.src_xyz + (size_t)pt * 3;
-            float q0 = p[0], q1 = p[1], q2 = p[2];
-            if (x.ctr_xyz) {
-                const float* cp = x.ctr_xyz + (size_t)grp * 3;
-                q0 = __fsub_rn(q0, cp[0]); q1 = __fsub_rn(q1, cp[1]); q2 = __fsub_rn(q2, cp[2]);
-            }
-            float a[4] = {0.f, 0.f, 0.f, 0.f};
-            const int t0 = c - x.feat_c;
-            if (x.action) {
-                const float* ap = x.action + (size_t)(grp / x.gps) * x.act_c;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int ai = t0 + j - 3;
-                    const int aic = ai < 0 ? 0 : (ai >= x.act_c ? x.act_c - 1 : ai);
-                    const float av = ap[aic];
-                    a[j] = (ai >= 0 && ai < x.act_c) ? av : 0.f;
-                }
-            }
-            float* spv = &o.s.x;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int t = t0 + j;
-                spv[j] = t == 0 ? q0 : (t == 1 ? q1 : (t == 2 ? q2 : a[j]));
-            }
-        }
-    }
-    return o;
-}
-
-// sv/tv: the layer-input BatchNorm scale/shift of this group's channels, staged in LDS
-template <int XM>
-__device__ __forceinline__ float4 x_finish(const XSrc& x, const XRaw& raw, bool valid, int c, const float* sv,
-                                           const float* tv) {
-    const int bulk = XM == 0 ? x.c_in : x.feat_c;
-    const bool inside = c < bulk;
-    float4 v = raw.a;
-    if (XM == 0) {
-        const int cc = inside ? c : x.c_in - 4;
-        if (x.affine) {
-            const float4 s = *reinterpret_cast<const float4*>(sv + cc), t = *reinterpret_cast<const float4*>(tv + cc);
-            v.x = fmaf(v.x, s.x, t.x); v.y = fmaf(v.y, s.y, t.y); v.z = fmaf(v.z, s.z, t.z); v.w = fmaf(v.w, s.w, t.w);
-        }
-        if (x.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-    }
-    return f4sel(valid, f4sel(inside, v, raw.s), f4zero());
-}
-
-__device__ __forceinline__ void stage_vec(float* dst, const float* src, int off, int n, float fill) {
-    for (int i = threadIdx.x; i < n; i += 256) dst[i] = src ? src[off + i] : fill;
-}
-
-struct DzSrc {   // gad_dz_src on the device
-    const float* z; int z_pitch; const float* scale; const float* shift; int relu;
-    const float* P; const float* Q; const float* S; const float* row_w;
-    int gmode; const float* G; int g_pitch; const int32_t* argmax; const float* dout;
-    const int32_t* row_grp; int c;
-    int coef;            // BatchNorm backward applies (P/Q/S given, or formed here from bw)
-    int premasked;       // the ReLU mask is already in G / dout
-    gad_bn_bwd bw;       // bw.dbeta != NULL: P, Q, S are formed by this launch from the layer's f64 sums
-};
-
-static DzSrc make_dzsrc(const gad_dz_src& d) {
-    DzSrc s;
-    s.z = d.z; s.z_pitch = d.z_pitch; s.scale = d.scale; s.shift = d.shift; s.relu = d.relu;
-    s.P = d.coefP; s.Q = d.coefQ; s.S = d.coefS; s.row_w = d.row_w;
-    s.gmode = d.gmode; s.G = d.G; s.g_pitch = d.g_pitch; s.argmax = d.argmax; s.dout = d.dout;
-    s.row_grp = d.row_grp; s.c = d.c;
-    s.premasked = d.premasked;
-    s.bw.dbeta = d.bn_dbeta; s.bw.dgamma = d.bn_dgamma; s.bw.stat_stride = d.bn_stride; s.bw.count = d.bn_count;
-    s.bw.mean = d.bn_mean; s.bw.istd = d.bn_istd; s.bw.gacc_gamma = d.gacc_gamma; s.bw.gacc_beta = d.gacc_beta;
-    s.bw.accumulate = (d.gacc_gamma || d.gacc_beta) ? 1 : 0;
-    s.coef = (d.coefP != nullptr || d.bn_dbeta != nullptr) ? 1 : 0;
-    return s;
-}
-
-// P, Q, S of channel ch (identity when the layer has no BatchNorm)
-// `writer`: this thread is the launch's one thread for channel ch that may add dgamma / dbeta to the gradient arena
-__device__ __forceinline__ void dz_coef(const DzSrc& d, int ch, float& P, float& Q, float& S, bool writer = false) {
-    if (d.bw.dbeta) gad_bn_bwd_channel(d.bw, d.scale, ch, writer, P, Q, S);
-    else if (d.P) { P = d.P[ch]; Q = d.Q[ch]; S = d.S[ch]; }
-    else { P = 1.f; Q = 0.f; S = 0.f; }
-}
-__device__ __forceinline__ bool first_workgroup() { return blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0; }
-
-struct DzRaw { float4 z; float4 g; int4 a; };
-
-// scalar (unaligned) evaluation of dZ[r][n..n+3], used for the tiny last layers of the heads
-__device__ __forceinline__ float4 dz_scalar4(const DzSrc& d, int r, bool valid, int off, int n, int nmax) {
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int nn = n + j;
-        const bool ok = valid && nn < nmax;
-        const int rr = ok ? r : 0;
-        const int ch = off + (ok ? nn : 0);
-        float z = 0.f;
-        if (d.z) z = d.z[(size_t)rr * d.z_pitch + ch];
-        float g;
-        if (d.gmode == 0) {
-            g = d.G[(size_t)rr * d.g_pitch + ch];
-        } else {
-            const int grp = d.row_grp[rr];
-            g = d.argmax[(size_t)grp * d.c + ch] == r ? d.dout[(size_t)grp * d.c + ch] : 0.f;
-        }
-        if (d.relu && !d.premasked) {
-            const float y = d.scale ? fmaf(z, d.scale[ch], d.shift[ch]) : z;
-            g = y > 0.f ? g : 0.f;
-        }
-        if (d.P) {
-            const float w = d.row_w ? d.row_w[rr] : 1.f;
-            g = d.P[ch] * g - w * fmaf(d.S[ch], z, d.Q[ch]);
-        }
-        v[j] = ok ? g : 0.f;
-    }
-    return make_float4(v[0], v[1], v[2], v[3]);
-}
-
-// raw loads of dZ's ingredients for row r, channels off+n..+3 (VEC: everything 16-byte aligned)
-template <bool VEC>
-__device__ __forceinline__ DzRaw dz_raw(const DzSrc& d, int r, bool valid, int off, int n, int nmax, int grp) {
-    DzRaw o;
-    o.z = f4zero(); o.a = make_int4(0, 0, 0, 0);
-    if (!VEC) { o.g = dz_scalar4(d, r, valid, off, n, nmax); return o; }
-    const int rr = valid ? r : 0;
-    const int ch = off + (n < nmax ? n : 0);
-    if (d.z) o.z = ldg4(d.z + (size_t)rr * d.z_pitch + ch);
-    if (d.gmode == 0) {
-        o.g = ldg4(d.G + (size_t)rr * d.g_pitch + ch);
-    } else {
-        o.a = *reinterpret_cast<const int4*>(d.argmax + (size_t)grp * d.c + ch);
-        o.g = ldg4(d.dout + (size_t)grp * d.c + ch);
-    }
-    return o;
-}
-
-// vec: LDS copies of {scale, shift, P, Q, S} of this group's channels (VM floats each; VM = VMAX unless the kernel sizes its LDS for narrower layers)
-template <bool VEC, int VM = VMAX>
-__device__ __forceinline__ float4 dz_finish(const DzSrc& d, const DzRaw& raw, int r, bool valid, int n, int nmax, float w,
-                                            const float* vec) {
-    if (!VEC) return raw.g;
-    const bool inside = n < nmax;
-    const int nn = inside ? n : 0;
-    float4 g = raw.g;
-    const float4 z = raw.z;
-    if (d.gmode != 0) {
-        g.x = raw.a.x == r ? g.x : 0.f; g.y = raw.a.y == r ? g.y : 0.f;
-        g.z = raw.a.z == r ? g.z : 0.f; g.w = raw.a.w == r ? g.w : 0.f;
-    }
-    if (d.relu && !d.premasked) {
-        float4 y = z;
-        if (d.scale) {
-            const float4 s = *reinterpret_cast<const float4*>(vec + nn), t = *reinterpret_cast<const float4*>(vec + VM + nn);
-            y.x = fmaf(z.x, s.x, t.x); y.y = fmaf(z.y, s.y, t.y); y.z = fmaf(z.z, s.z, t.z); y.w = fmaf(z.w, s.w, t.w);
-        }
-        g.x = y.x > 0.f ? g.x : 0.f; g.y = y.y > 0.f ? g.y : 0.f;
-        g.z = y.z > 0.f ? g.z : 0.f; g.w = y.w > 0.f ? g.w : 0.f;
-    }
-    if (d.coef) {
-        const float4 P = *reinterpret_cast<const float4*>(vec + 2 * VM + nn);
-        const float4 Q = *reinterpret_cast<const float4*>(vec + 3 * VM + nn);
-        const float4 S = *reinterpret_cast<const float4*>(vec + 4 * VM + nn);
-        g.x = P.x * g.x - w * fmaf(S.x, z.x, Q.x); g.y = P.y * g.y - w * fmaf(S.y, z.y, Q.y);
-        g.z = P.z * g.z - w * fmaf(S.z, z.z, Q.z); g.w = P.w * g.w - w * fmaf(S.w, z.w, Q.w);
-    }
-    return f4sel(valid && inside, g, f4zero());
-}
-
-template <int VM = VMAX>
-__device__ __forceinline__ void stage_dz_vecs(float* vec, const DzSrc& d, int off, int n) {
-    if (!d.premasked) {
-        stage_vec(vec, d.scale, off, n, 1.f);
-        stage_vec(vec + VM, d.shift, off, n, 0.f);
-    }
-    for (int i = threadIdx.x; i < n; i += 256) {
-        float P, Q, S;
-        dz_coef(d, off + i, P, Q, S, first_workgroup());
-        vec[2 * VM + i] = P; vec[3 * VM + i] = Q; vec[4 * VM + i] = S;
-    }
-}
-
-static bool dz_vectorizable(const gad_dz_src& d, const int32_t* off, const int32_t* n_out, int ng) {
-    bool ok = (d.z == nullptr || d.z_pitch % 4 == 0) && (d.gmode != 0 || d.g_pitch % 4 == 0) && (d.gmode == 0 || d.c % 4 == 0);
-    for (int i = 0; i < ng; ++i) ok = ok && off[i] % 4 == 0 && n_out[i] % 4 == 0 && n_out[i] <= VMAX;
-    return ok;
-}
-
-// ------------------------------------------------------------------------------------------------
-// LDS tile helpers.  Tiles are k-major: T[kk][i], kk in [0,KT), i in [0,DIM).
-//   transposing store (source contiguous along kk): pitch DIM+1, four ds_write_b32
-//   direct store      (source contiguous along i) : pitch DIM+4, one ds_write_b128
-// ------------------------------------------------------------------------------------------------
-template <int DIM> struct PitchT { static constexpr int v = DIM + 1; };
-template <int DIM> struct PitchD { static constexpr int v = DIM + 4; };
-
-template <int DIM> __device__ __forceinline__ void unit_T(int u, int& i, int& kk) { i = u >> 3; kk = (u & 7) << 2; }
-template <int DIM> __device__ __forceinline__ void unit_D(int u, int& kk, int& i) { kk = u / (DIM / 4); i = (u % (DIM / 4)) << 2; }
-
-template <int DIM> __device__ __forceinline__ void store_T(float* t, int i, int kk, float4 v) {
-    constexpr int P = PitchT<DIM>::v;
-    t[(kk + 0) * P + i] = v.x; t[(kk + 1) * P + i] = v.y; t[(kk + 2) * P + i] = v.z; t[(kk + 3) * P + i] = v.w;
-}
-template <int DIM> __device__ __forceinline__ void store_D(float* t, int kk, int i, float4 v) {
-    constexpr int P = PitchD<DIM>::v;
-    *reinterpret_cast<float4*>(t + kk * P + i) = v;
-}
-
-// One K-tile of MFMAs.  The operand fragments are read from LDS one CHUNK (4 k-steps) ahead of the MFMAs that
-// consume them: written naively (read, wait, MFMA) hipcc emits `ds_read; s_waitcnt lgkmcnt(0); v_mfma` per step and
-// a lone wavefront per SIMD (the small-M layers) spends as long waiting for LDS as issuing MFMAs.
-template <int TM, int TN, int PA, int PB>
-__device__ __forceinline__ void mfma_ktile(const float* __restrict__ As, const float* __restrict__ Bs, int am0,
-                                           int bn0, int lane, f32x16 (&acc)[TM][TN]) {
-    const int l31 = lane & 31, half = lane >> 5;
-    constexpr int CH = 4, NCH = KT / 2 / CH;
-    const float* ap = As + half * PA + am0 + l31;
-    const float* bp = Bs + half * PB + bn0 + l31;
-    float a[2][CH][TM], b[2][CH][TN];
-    auto fetch = [&](int c, int buf) {
-#pragma unroll
-        for (int s = 0; s < CH; ++s) {
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm) a[buf][s][tm] = ap[(2 * (c * CH + s)) * PA + tm * 32];
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn) b[buf][s][tn] = bp[(2 * (c * CH + s)) * PB + tn * 32];
-        }
-    };
-    fetch(0, 0);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        if (c + 1 < NCH) fetch(c + 1, (c + 1) & 1);
-        __builtin_amdgcn_sched_barrier(0);       // keep the next chunk's ds_reads ABOVE this chunk's MFMAs
-#pragma unroll
-        for (int s = 0; s < CH; ++s)
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn)
-                    acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c & 1][s][tm], b[c & 1][s][tn], acc[tm][tn], 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ int acc_row(int v, int half) { return (v & 3) + 8 * (v >> 2) + 4 * half; }
-
-// ------------------------------------------------------------------------------------------------
-// Segment max-pool folded into the epilogue of the pooled layer's GEMM (upstream _PointnetSAModuleBase.forward:
-// F.max_pool2d over the nsample axis of relu(bn(conv)); reference call site core/networks.py:66-81).
-// The pooled quantity is y = relu(scale * z + shift) with scale = gamma * istd: istd > 0, so the SIGN of scale is the sign
-// of gamma -- known before the layer's statistics exist -- and y is monotone in z.  The epilogue therefore reduces the RAW
-// output: max of sgn * z per (group, channel), sgn = +-1 from gamma; gad_pool_finalize applies the affine + ReLU to the
-// winner once the statistics are in (bit-identical to pooling y: a correctly rounded fma is monotone).
-// A group's rows are contiguous (CSR).  The output tile goes through LDS once so that a lane owns ONE column and walks the
-// rows in order: every lane of the wavefront sees the same rows, so the segment structure (where a group ends) is
-// wave-uniform -- scalar branches, group ids read with v_readlane -- and only the running maximum is per-lane work
-// (compare + two selects per row).  A group that lies inside the walked row range is written with ONE plain 8-byte store
-// per channel; only the groups cut by the range's ends (<= 2 per range) need a packed 64-bit atomic maximum --
-// key = (order-preserving bits of the value) << 32 | ~row, so among equal values the smaller row wins (the arg-max trick
-// of fps_kernel).  key 0 = "no row yet".  (First version: per-lane scan of the accumulator registers with an atomic per
-// segment -- 3-4 M atomics per SA1 / SA2 launch cost 20-35 us, profiles/README.md round 3.)
-// Arg-max rule vs the reference ("first maximal y"): identical unless two DIFFERENT raw values of a group round to the
-// same y (then the larger raw value wins here) -- gad_pool_finalize handles y <= 0 (every row ties at 0: first row).
-// ------------------------------------------------------------------------------------------------
-struct PoolEpi {
-    unsigned long long* key;       // (groups, C) packed keys, NULL: no pooling
-    const int32_t* row_grp;        // (rows) group of every row
-    const float* gamma;            // (C) BatchNorm weight of the pooled layer (its sign picks max / min)
-    int C;
-};
-
-__device__ __forceinline__ unsigned pool_ord(float f) {
-    const unsigned u = __float_as_uint(f);
-    return u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
-}
-
-// partial (wave-uniform): the group continues outside the rows this wavefront walks
-__device__ __forceinline__ void pool_put(unsigned long long* keycol, int g, int C, float v, int row, bool partial) {
-    const unsigned long long k = ((unsigned long long)pool_ord(v) << 32) | (unsigned long long)(0xffffffffu - (unsigned)row);
-    if (partial) atomicMax(keycol + (size_t)g * C, k);
-    else keycol[(size_t)g * C] = k;
-}
-
-// running state of one lane's column: the open group (uniform), whether it began before the walked range (uniform), the
-// best value so far and its row
-struct PoolRun { int g; int part; float v; int row; };
-
-// rows [i, e) of the LDS tile belong to the open group: running maximum of sgn * z, strict > (the first maximum stays),
-// for NC columns per lane (zt + c * cstride).  i, e, row_base are wave-uniform: the loads of a run are independent of the
-// compares and pipeline freely.
-template <int NC>
-__device__ __forceinline__ void pool_rows(const float* zt, int pitch, int cstride, int i, int e, int row_base, const float (&sgn)[NC],
-                                          float (&best)[NC], int (&brow)[NC]) {
-    int r = i;
-    for (; r + 2 <= e; r += 2) {
-        float z0[NC], z1[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) { z0[c] = zt[r * pitch + c * cstride] * sgn[c]; z1[c] = zt[(r + 1) * pitch + c * cstride] * sgn[c]; }
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            bool t = z0[c] > best[c]; best[c] = t ? z0[c] : best[c]; brow[c] = t ? row_base + r : brow[c];
-            t = z1[c] > best[c]; best[c] = t ? z1[c] : best[c]; brow[c] = t ? row_base + r + 1 : brow[c];
-        }
-    }
-    if (r < e) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const float z0 = zt[r * pitch + c * cstride] * sgn[c];
-            const bool t = z0 > best[c]; best[c] = t ? z0 : best[c]; brow[c] = t ? row_base + r : brow[c];
-        }
-    }
-}
-
-// One wavefront walks 32 consecutive rows (row_base ..) of its LDS tile, lane = column, carrying the open group across
-// calls (streaming kernel: a contiguous range of slabs per wavefront).  gl: lane i < 32 holds the group of row i (-1 past
-// the live rows).  A group that closes here is complete unless c.part says it began before the range.
-__device__ __forceinline__ void pool_scan32(const float* zt, int pitch, int gl, int row_base, float sgn, PoolRun& c,
-                                            unsigned long long* keycol, int C) {
-    const int lane = threadIdx.x & 63;
-    const int prev = __shfl_up(gl, 1, 64);
-    const bool st = lane == 0 ? gl != c.g : gl != prev;
-    const unsigned m = (unsigned)__ballot(st);                  // bit i: row i opens a group (c.g is wave-uniform)
-    int i = 0;
-    while (i < 32) {                                            // wave-uniform control flow throughout
-        if ((m >> i) & 1u) {
-            if (c.g >= 0) pool_put(keycol, c.g, C, c.v, c.row, c.part != 0);
-            c.g = __builtin_amdgcn_readlane(gl, i); c.part = 0; c.v = -INFINITY; c.row = row_base + i;
-        }
-        const unsigned rest = i < 31 ? m >> (i + 1) : 0u;
-        const int e = rest ? i + 1 + __builtin_ctz(rest) : 32;
-        if (c.g >= 0) {
-            const float sg1[1] = {sgn};
-            float bv[1] = {c.v};
-            int br[1] = {c.row};
-            pool_rows<1>(zt, pitch, 0, i, e, row_base, sg1, bv, br);
-            c.v = bv[0]; c.row = br[0];
-        }
-        i = e;
-    }
-}
-
-// A 64-row tile in LDS, lane = column (NC columns per lane, cstride apart), the tile's groups dealt to the workgroup's
-// wavefronts (piece k -> wavefront k % nw): every piece is closed by the wavefront that walked it; only the pieces cut by
-// the tile's first / last row are partial.
-// gl: lane i holds the group of tile row i (-1 past the live rows); n_live = live rows of the tile (>= 1); g_before /
-// g_after: the groups of the rows just outside the tile (-1: none) -- a piece that shares its group with them is partial.
-template <int NC>
-__device__ __forceinline__ void pool_tile64(const float* zt, int pitch, int cstride, int gl, int row0, int n_live,
-                                            const float (&sgn)[NC], int wave, int nw, int g_before, int g_after,
-                                            unsigned long long* keycol, int C) {
-    const int lane = threadIdx.x & 63;
-    const int prev = __shfl_up(gl, 1, 64);
-    const bool st = (lane == 0 || gl != prev) && lane < n_live;
-    unsigned long long m = __ballot(st);
-    int k = 0;
-    while (m) {                                                 // wave-uniform
-        const int i = __builtin_ctzll(m);
-        m &= m - 1;
-        const int e = m ? __builtin_ctzll(m) : n_live;
-        if ((k++ % nw) != wave) continue;
-        const int g = __builtin_amdgcn_readlane(gl, i);
-        float best[NC];
-        int brow[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) { best[c] = -INFINITY; brow[c] = row0 + i; }
-        pool_rows<NC>(zt, pitch, cstride, i, e, row0, sgn, best, brow);
-        const bool partial = (i == 0 && g == g_before) || (e == n_live && g == g_after);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) pool_put(keycol + c * cstride, g, C, best[c], brow[c], partial);
-    }
-}
-
-struct Groups {
-    int n; int aoff[GAD_MAX_GROUPS]; int woff[GAD_MAX_GROUPS]; int ooff[GAD_MAX_GROUPS]; int nout[GAD_MAX_GROUPS];
-};
-
-// per-column partial sums held by lanes 0..31 of each wavefront -> one f64 atomic per column and block (STORE: the deterministic
-// mode's plain store of the block's partial into its own slot, out0 / out1 = that slot)
-template <int WM, int WN, int TN, bool STORE = false>
-__device__ __forceinline__ void block_column_atomics(float* red, const float (&c0)[TN], const float (&c1)[TN], int lane,
-                                                     int wm, int wn, int col0, int col_limit, double* out0,
-                                                     double* out1) {
-    constexpr int BN = WN * TN * 32;
-    __syncthreads();
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-        const float s0 = c0[tn] + __shfl_xor(c0[tn], 32, 64);
-        const float s1 = c1[tn] + __shfl_xor(c1[tn], 32, 64);
-        if (lane < 32) {
-            const int cl = wn * TN * 32 + tn * 32 + lane;
-            red[wm * BN + cl] = s0;
-            red[(WM + wm) * BN + cl] = s1;
-        }
-    }
-    __syncthreads();
-    const int tid = threadIdx.x;
-    if (tid < BN && col0 + tid < col_limit) {
-        float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-        for (int w = 0; w < WM; ++w) { s0 += red[w * BN + tid]; s1 += red[(WM + w) * BN + tid]; }
-        if (STORE) {
-            out0[col0 + tid] = (double)s0;
-            out1[col0 + tid] = (double)s1;
-        } else {
-            atomic_add_f64(out0 + col0 + tid, (double)s0);
-            atomic_add_f64(out1 + col0 + tid, (double)s1);
-        }
-    }
+bool split_on(int family) {
+    return !g_opt.deterministic && (g_opt.mfma_split == GAD_SPLIT_ALL || (g_opt.mfma_split & family) != 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -746,117 +199,6 @@ __global__ __launch_bounds__(256) void gemm_fwd_kernel(XSrc x, Groups gr, const 
                                               stat_sq + (size_t)rep * stat_stride + ooff);
     }
 }
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// ---- split-bf16 arithmetic (library option "mfma_split": a mask of kernel families, include/gaddpg.h GAD_SPLIT_*) ----
-// An f32 value = hi + mid + lo, three bf16 terms of 8 significand bits each (the residuals are exact f32 subtractions); a product of
-// two such values to 24 bits = the six term products of weight >= 2^-16, each exact in the f32 accumulator of
-// v_mfma_f32_32x32x16_bf16 (16x the rate of v_mfma_f32_32x32x2_f32).  The bf16 MFMA's adder truncates toward -inf (a -1e-8
-// relative bias, tools/ubench/split_bf16.hip): the products of every second block of 16 along the reduction index are
-// NEGATED (one operand's sign) and summed into a second accumulator; result = plain - negated, which cancels the bias and
-// leaves a smaller random error than the f32 MFMA's (profiles/r04_split_bf16_ubench.txt).  The cancellation is exact only
-// where the two accumulators sit in the same binade; what is left (~2e-11 of max |z| per element) has a sign that depends on
-// the output COLUMN (which half of a column's weights is larger), so a sum over the rows of one column -- BatchNorm statistics,
-// dbeta -- would add it coherently.  The kernels whose outputs are summed over rows therefore also negate the A operand of
-// every ODD ROW and take (negated - plain) there: the residual changes sign from row to row and averages out
-// (profiles/r05_split_families.txt).
-// Range: |x| must stay below 3.39e38 (bf16(x) must not round to infinity); an infinite operand gives NaN where the f32
-// path gives +-inf (both non-finite).
-typedef __bf16 gad_bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ unsigned gad_cvt_pk_bf16(float lo, float hi) {     // {bf16(hi), bf16(lo)}, round to nearest even
-    unsigned r;
-    __asm__("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-__device__ __forceinline__ void gad_split2(float a, float b, unsigned& H, unsigned& M, unsigned& L) {
-    H = gad_cvt_pk_bf16(a, b);
-    const f32x2 r = f32x2{a, b} - f32x2{__uint_as_float(H << 16), __uint_as_float(H & 0xffff0000u)};
-    M = gad_cvt_pk_bf16(r.x, r.y);
-    const f32x2 q = r - f32x2{__uint_as_float(M << 16), __uint_as_float(M & 0xffff0000u)};
-    L = gad_cvt_pk_bf16(q.x, q.y);
-}
-__device__ __forceinline__ gad_bf16x8 gad_as_bf16x8(gad_u32x4 u) { return *reinterpret_cast<gad_bf16x8*>(&u); }
-
-// family mask (GAD_SPLIT_*; 1 = all): which GEMM families multiply as split-bf16 MFMAs.  LIBRARY default 0 = v_mfma_f32_32x32x2_f32
-// throughout (round 6, ADVICE r05: a caller of the C ABI gets the reference's arithmetic unless it asks for something else); the
-// Python package opts in explicitly when it loads the library (ga-ddpg_amd/hip.py OPTION_DEFAULTS: GAD_SPLIT_ALL -- the per-family
-// float64 gates of tests/test_gpu_split_families.py, the range / specials tests and every oracle-facing gate in both modes are green
-// on MI355X), GAD_OPT_mfma_split=0 keeps the f32 MFMA.  Precondition of the split form: finite operands below 3.39e38 in magnitude
-// (bf16(x) must not round to infinity; an infinite operand gives NaN where the f32 path gives +-inf).
-static int g_opt_mfma_split = 0;
-static int g_opt_deterministic = 0;       // option "deterministic": the generic tile kernels only, ordered partial sums (below gad_set_option)
-static bool split_on(int family) {
-    return !g_opt_deterministic && (g_opt_mfma_split == GAD_SPLIT_ALL || (g_opt_mfma_split & family) != 0);
-}
-
-// Wide-tile kernels in split form (gemm_fwd_wide / gemm_dx_wide with SP): a 64 x 128 block tile per 4-wavefront workgroup,
-// K-tile 32.  Both operand tiles live in LDS as three bf16 planes of 64-byte rows (32 reduction indices), double-buffered:
-//   stage = A planes 3 x 64 rows | B planes 3 x 128 rows = 36 KB;
-// a row's four 16-byte chunks are XOR-swizzled by (row >> 2) & 3, so the fragment reads -- lane (row l31, half) takes chunk
-// 2 s + half of k16-step s: one ds_read_b128 = the 8 consecutive reduction indices v_mfma_f32_32x32x16_bf16 wants per lane --
-// are conflict-free without padding (every 16-lane group of the instruction covers 16 rows that differ mod 16), and so are
-// the staging stores (ds_write_b64 for the A side, split in registers; ds_write_b128 for the B side, copied from the
-// pre-split weight mirror).  k16-step 0 of a K-tile accumulates into `acc`, step 1 -- whose mirror values are stored negated --
-// into `an`.
-namespace spw {
-constexpr int APL = 64 * 64, BPL = 128 * 64, STAGE = 3 * (APL + BPL);       // bytes
-struct BRegs { gad_u32x4 r[2][3]; };
-// this thread's B chunks of K-tile kt: rows (tid >> 2) + 64 u of the block's 128 mirror rows, chunk tid & 3
-__device__ __forceinline__ void load_b(BRegs& b, __amdgpu_buffer_rsrc_t rs, const int (&vb)[2], int plane_bytes, int kt) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) b.r[u][p] = __builtin_amdgcn_raw_buffer_load_b128(rs, vb[u], p * plane_bytes + kt * 64, 0);
-}
-__device__ __forceinline__ void store_b(unsigned char* stage, const BRegs& b, int tid) {
-    const int row = tid >> 2;
-    unsigned char* q = stage + 3 * APL + row * 64 + ((((tid & 3) ^ ((row >> 2) & 3))) << 4);
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) *reinterpret_cast<gad_u32x4*>(q + p * BPL + u * (64 * 64)) = b.r[u][p];
-}
-// four consecutive reduction indices (c4 = (tid & 7) * 4 of the K-tile) of A row `row` -> the three planes (8 bytes each)
-// sg: 0x80000000 for an odd row (its values enter negated, the epilogue takes negated - plain), else 0
-__device__ __forceinline__ void store_a4(unsigned char* stage, int row, int tid, float4 v, unsigned sg) {
-    unsigned h0, m0, l0, h1, m1, l1;
-    gad_split2(__uint_as_float(__float_as_uint(v.x) ^ sg), __uint_as_float(__float_as_uint(v.y) ^ sg), h0, m0, l0);
-    gad_split2(__uint_as_float(__float_as_uint(v.z) ^ sg), __uint_as_float(__float_as_uint(v.w) ^ sg), h1, m1, l1);
-    unsigned char* q = stage + row * 64 + (((((tid & 7) >> 1) ^ ((row >> 2) & 3))) << 4) + ((tid & 1) << 3);
-    *reinterpret_cast<uint2*>(q) = make_uint2(h0, h1);
-    *reinterpret_cast<uint2*>(q + APL) = make_uint2(m0, m1);
-    *reinterpret_cast<uint2*>(q + 2 * APL) = make_uint2(l0, l1);
-}
-// MFMAs of one staged K-tile for the wavefront's 32 x 64 tile: arow / brow = byte offsets of the lane's A row and first B row
-// inside the stage, fo = ((half ^ swizzle) << 4) -- the lane's chunk of k16-step 0; step 1's is fo ^ 32
-__device__ __forceinline__ void ktile(const unsigned char* stage, int arow, int brow, int fo, f32x16 (&acc)[2], f32x16 (&an)[2]) {
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const int off = fo ^ (s << 5);
-        const unsigned char* ap = stage + arow + off;
-        const unsigned char* bp = stage + 3 * APL + brow + off;
-        const gad_u32x4 AH = *reinterpret_cast<const gad_u32x4*>(ap), AM = *reinterpret_cast<const gad_u32x4*>(ap + APL);
-        const gad_u32x4 AL = *reinterpret_cast<const gad_u32x4*>(ap + 2 * APL);
-        gad_u32x4 BH[2], BM[2], BL[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            BH[t] = *reinterpret_cast<const gad_u32x4*>(bp + t * (32 * 64));
-            BM[t] = *reinterpret_cast<const gad_u32x4*>(bp + BPL + t * (32 * 64));
-            BL[t] = *reinterpret_cast<const gad_u32x4*>(bp + 2 * BPL + t * (32 * 64));
-        }
-        // the six products of weight >= 2^-16, smallest first
-#define GAD_SPW(A, B)                                                                                                          \
-        _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                                                        \
-            if (s) an[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gad_as_bf16x8(A), gad_as_bf16x8(B[t]), an[t], 0, 0, 0);     \
-            else acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gad_as_bf16x8(A), gad_as_bf16x8(B[t]), acc[t], 0, 0, 0);     \
-        }
-        GAD_SPW(AL, BH) GAD_SPW(AH, BL) GAD_SPW(AM, BM) GAD_SPW(AM, BH) GAD_SPW(AH, BM) GAD_SPW(AH, BH)
-#undef GAD_SPW
-    }
-}
-}  // namespace spw
-
 // ------------------------------------------------------------------------------------------------
 // wide-tile forward for the MID-SIZE layers (SA2 / SA3 layers 2 and 3: 8e3 - 3e4 rows, K 128 - 256, 128 - 512 outputs).
 // The 64 x 64 kernel above gives every wavefront ONE 32 x 32 accumulator: 16 MFMAs (0.45 us) per K-tile against ~1 us of
@@ -1152,24 +494,17 @@ __global__ __launch_bounds__(256, 2) void gemm_fwd_wide_kernel(XSrc x, const int
 #endif
 }
 
-static int g_opt_fwd_wide = 1;
-static int g_opt_dx_wide = 1, g_opt_dw_wide = 1;
-static int g_opt_bwd_fused = 1;
-static int g_opt_fwd_bn_prologue = 1;           // 0: routes with a BatchNorm-finalising prologue launch gad_bn_finalize instead (A/B)
-static int g_opt_bwd_wide = 0;                  // fused wide backward: 0 off (default: slower in the step), 1 SA2 and SA3 shapes, 2 only layers with >= 16384 rows (SA2)
-static int g_opt_bwd_wide_slab = 4;             // most partial-dW elements (millions) a fused launch may write: bounds its workgroups per k block
-static int g_opt_dw_wide_wgs = 256;        // workgroups a wide-tile dW launch aims for (its partial slab = this x 128 x 128 floats)
 // the wide-tile kernel covers: ACT input, one group, K = the channel count itself (a multiple of 32, no bias / extra
 // column), outputs a multiple of 128
 static bool fits_i32_bytes(long long rows, int pitch_a, int pitch_b, int pitch_c, int pitch_d);
 static bool fwd_wideable(const gad_gemm_fwd_args& a) {
-    if (g_opt_deterministic || !g_opt_fwd_wide || a.n_groups != 1 || a.zin_off[0] != 0 || a.w_off[0] != 0 || a.out_off[0] != 0) return false;
+    if (g_opt.deterministic || !g_opt.fwd_wide || a.n_groups != 1 || a.zin_off[0] != 0 || a.w_off[0] != 0 || a.out_off[0] != 0) return false;
     // (gathered input: the point-major feature tensor has at most as many rows as there are (group, point) rows upstream)
     if (!fits_i32_bytes(a.n_rows, a.mode == 1 ? a.feat_c : a.zin_pitch, a.zout ? a.zout_pitch : 0, 0, 0)) return false;
     if (a.n_rows < 2048 || a.n_out[0] % 128 != 0 || a.ones_col >= 0) return false;
     if (a.mode == 2) return false;
     if (a.mode == 1)                                     // gathered first layer: features a multiple of 32, + 3 coordinates
-        return g_opt_fwd_wide != 2 && !a.pool_key && a.act_c == 0 && a.feat_c % 32 == 0 && a.feat_c >= 32 && a.feat_c <= 512 &&
+        return g_opt.fwd_wide != 2 && !a.pool_key && a.act_c == 0 && a.feat_c % 32 == 0 && a.feat_c >= 32 && a.feat_c <= 512 &&
                a.Kp == ((a.feat_c + 3 + 7) & ~7);
     if (a.Kp % 32 != 0 || a.Kp > 512 || a.Kp != a.c_in) return false;
     return !a.extra && a.scale && a.shift && a.relu;
@@ -1610,11 +945,6 @@ __global__ __launch_bounds__(512, 2) void gemm_fwd_stream_kernel(XSrc x, const i
 // streaming kernel, no LDS staging, no barrier) before its first MFMA, so the load latency is paid about once;
 // the partial tiles are summed through LDS.  256 rows x 1024 -> 512: 37.8 us -> see tools/diag_gemm.py.
 // ------------------------------------------------------------------------------------------------
-#define SK_NW 8          // wavefronts per workgroup (K split); 16 -> 128-VGPR budget -> spills, 2x slower
-#define SK_CH 6          // 8-wide k groups per register chunk (17 x 1 = the whole K share in one round of loads: measured 2 % slower)
-#define SK_SP 36         // pitch (floats) of the wavefront-private operand stage of the skinny forward kernel
-#define SK_KCAP (8 * SK_NW * SK_CH * SK_MAXCH)   // most input channels of a skinny launch (per-channel affine staged in LDS)
-#define SK_MAXCH 3       // chunks per wavefront: K <= 8 * SK_NW * SK_CH * SK_MAXCH = 1152
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void gemm_fwd_skinny_kernel(XSrc x, Groups gr, int n_rows,
                                                                      const float* __restrict__ row_w,
@@ -1759,19 +1089,9 @@ __global__ __launch_bounds__(64 * NW) void gemm_fwd_skinny_kernel(XSrc x, Groups
     }
 }
 
-#define GAD_GX_CAP 2048           // most row tiles a tile launch spreads over workgroups (the rest by its grid-stride loop)
-static int g_opt_skinny_nw = SK_NW;    // wavefronts per skinny workgroup: 8, or 4 (A/B: a quarter of a CU's registers and < 60 KB of LDS, so a workgroup fits beside the side lanes' wide kernels)
-static int g_opt_fwd_skinny = 1, g_opt_dx_skinny = 1, g_opt_dx_stream = 1, g_opt_dw_skinny = 1, g_opt_dw_stream = 1;
 static bool fwd_skinny(const gad_gemm_fwd_args& a) {
-    return !g_opt_deterministic && g_opt_fwd_skinny && a.mode == 0 && !a.n_rows_dev && a.n_rows <= 1024 && a.Kp <= SK_KCAP;
+    return !g_opt.deterministic && g_opt.fwd_skinny && a.mode == 0 && !a.n_rows_dev && a.n_rows <= 1024 && a.Kp <= SK_KCAP;
 }
-
-
-static int g_opt_fwd_stream = 1;
-#define DW_STREAM_SPLITS 256
-static int g_opt_bwd_stream_wgs = DW_STREAM_SPLITS;   // persistent workgroups (= partial dW blocks) of the fused SA1 backward: A/B, <= DW_STREAM_SPLITS
-static int g_opt_fwd_stream_wgs = 256;         // persistent workgroups of the streaming forward's layers 2 / 3 (A/B: fewer leave CUs to the sibling pass's small launches)
-static int g_opt_fwd_stream_l1_wgs = 256;      // persistent workgroups of the streaming forward's gathered first layer (A/B: 512 = two per CU)
 
 // ---- deterministic mode (option "deterministic"; include/gaddpg.h) ----
 // Routing: the generic tile kernels only (every family predicate below answers false, split-bf16 off, gad_gemm_bwd unfused); their
@@ -1779,7 +1099,7 @@ static int g_opt_fwd_stream_l1_wgs = 256;      // persistent workgroups of the s
 // row CAPACITY only: grid-rows hints are ignored) and one ordered column reduce (ordered_reduce_kernel) that adds the slot sums, in
 // slot order, into replica 0 of the statistics or into the gradient arena.  The gathered first layers store each row's input
 // gradient and ordered kernels walk the rows: point-disjoint runs for dfeat, samples for daction.  No memory is allocated here.
-int gad_deterministic() { return g_opt_deterministic; }
+int gad_deterministic() { return g_opt.deterministic; }
 
 namespace {
 struct DetBuf { void* stream; int kind; void* p; size_t bytes; };
@@ -1876,32 +1196,41 @@ int gad_ordered_reduce(const double* slots, long long slot_stride, int nslots, l
     return ordered_reduce_launch(slots, slot_stride, nslots, ncols, out, stream);
 }
 
+// every GEMM option: a value inside [lo, hi] is taken as given, any other becomes `fallback` (ANY_LO .. ANY_HI: every int is taken)
+constexpr int ANY_LO = -2147483647 - 1, ANY_HI = 2147483647;
+static const struct { const char* name; int GemmOptions::*member; int lo, hi, fallback; } k_options[] = {
+    {"deterministic", &GemmOptions::deterministic, 0, 0, 1},       // normalised: 0 is taken, everything else becomes 1
+    {"mfma_split", &GemmOptions::mfma_split, ANY_LO, ANY_HI, 0},
+    {"fwd_stream", &GemmOptions::fwd_stream, ANY_LO, ANY_HI, 0},
+    {"fwd_wide", &GemmOptions::fwd_wide, ANY_LO, ANY_HI, 0},
+    {"dx_wide", &GemmOptions::dx_wide, ANY_LO, ANY_HI, 0},
+    {"dw_wide", &GemmOptions::dw_wide, ANY_LO, ANY_HI, 0},
+    {"bwd_fused", &GemmOptions::bwd_fused, ANY_LO, ANY_HI, 0},
+    {"bwd_wide", &GemmOptions::bwd_wide, ANY_LO, ANY_HI, 0},
+    {"fwd_bn_prologue", &GemmOptions::fwd_bn_prologue, ANY_LO, ANY_HI, 0},
+    {"fwd_skinny", &GemmOptions::fwd_skinny, ANY_LO, ANY_HI, 0},
+    {"dx_skinny", &GemmOptions::dx_skinny, ANY_LO, ANY_HI, 0},
+    {"dx_stream", &GemmOptions::dx_stream, ANY_LO, ANY_HI, 0},
+    {"dw_skinny", &GemmOptions::dw_skinny, ANY_LO, ANY_HI, 0},
+    {"dw_stream", &GemmOptions::dw_stream, ANY_LO, ANY_HI, 0},
+    {"bwd_stream_wgs", &GemmOptions::bwd_stream_wgs, 1, DW_STREAM_SPLITS, DW_STREAM_SPLITS},
+    {"fwd_stream_wgs", &GemmOptions::fwd_stream_wgs, 1, 2147483647, 256},
+    {"fwd_stream_l1_wgs", &GemmOptions::fwd_stream_l1_wgs, 1, 2147483647, 256},
+    {"dw_wide_wgs", &GemmOptions::dw_wide_wgs, 1, 2147483647, 256},
+    {"bwd_wide_slab", &GemmOptions::bwd_wide_slab, 1, 2147483647, 4},
+    {"skinny_nw", &GemmOptions::skinny_nw, 4, 4, SK_NW},            // 4 is taken, everything else becomes SK_NW (8)
+};
+
 extern "C" int gad_set_option(const char* name, int value) {
     GAD_REQUIRE(name, GAD_ERR_NULL, "set_option: null name");
-    if (!strcmp(name, "deterministic")) {
-        if (!value && g_opt_deterministic) det_scratch_release();
-        g_opt_deterministic = value ? 1 : 0;
+    for (const auto& o : k_options) {
+        if (strcmp(name, o.name)) continue;
+        const int v = (value >= o.lo && value <= o.hi) ? value : o.fallback;
+        // (the one option with a side effect: switching the deterministic mode off frees its scratch)
+        if (o.member == &GemmOptions::deterministic && !v && g_opt.deterministic) det_scratch_release();
+        g_opt.*o.member = v;
         return GAD_OK;
     }
-    if (!strcmp(name, "fwd_stream")) { g_opt_fwd_stream = value; return GAD_OK; }
-    if (!strcmp(name, "bwd_stream_wgs")) { g_opt_bwd_stream_wgs = (value > 0 && value <= DW_STREAM_SPLITS) ? value : DW_STREAM_SPLITS; return GAD_OK; }
-    if (!strcmp(name, "fwd_stream_wgs")) { g_opt_fwd_stream_wgs = value > 0 ? value : 256; return GAD_OK; }
-    if (!strcmp(name, "fwd_stream_l1_wgs")) { g_opt_fwd_stream_l1_wgs = value > 0 ? value : 256; return GAD_OK; }
-    if (!strcmp(name, "fwd_wide")) { g_opt_fwd_wide = value; return GAD_OK; }
-    if (!strcmp(name, "dx_wide")) { g_opt_dx_wide = value; return GAD_OK; }
-    if (!strcmp(name, "dw_wide")) { g_opt_dw_wide = value; return GAD_OK; }
-    if (!strcmp(name, "bwd_fused")) { g_opt_bwd_fused = value; return GAD_OK; }
-    if (!strcmp(name, "bwd_wide")) { g_opt_bwd_wide = value; return GAD_OK; }
-    if (!strcmp(name, "fwd_bn_prologue")) { g_opt_fwd_bn_prologue = value; return GAD_OK; }
-    if (!strcmp(name, "bwd_wide_slab")) { g_opt_bwd_wide_slab = value > 0 ? value : 4; return GAD_OK; }
-    if (!strcmp(name, "mfma_split")) { g_opt_mfma_split = value; return GAD_OK; }
-    if (!strcmp(name, "dw_wide_wgs")) { g_opt_dw_wide_wgs = value > 0 ? value : 256; return GAD_OK; }
-    if (!strcmp(name, "skinny_nw")) { g_opt_skinny_nw = value == 4 ? 4 : SK_NW; return GAD_OK; }
-    if (!strcmp(name, "fwd_skinny")) { g_opt_fwd_skinny = value; return GAD_OK; }
-    if (!strcmp(name, "dx_skinny")) { g_opt_dx_skinny = value; return GAD_OK; }
-    if (!strcmp(name, "dx_stream")) { g_opt_dx_stream = value; return GAD_OK; }
-    if (!strcmp(name, "dw_skinny")) { g_opt_dw_skinny = value; return GAD_OK; }
-    if (!strcmp(name, "dw_stream")) { g_opt_dw_stream = value; return GAD_OK; }
     int found = 0;
     gad_geometry_set_option(name, value, &found);                                     // geometry.hip: "bq_cells"
     if (found) return GAD_OK;
@@ -1911,7 +1240,7 @@ extern "C" int gad_set_option(const char* name, int value) {
 
 // the streaming kernel covers: one group, no bias / extra column, Kp in {16, 64}, n_out in {64, 128}
 static bool fwd_streamable(const gad_gemm_fwd_args& a) {
-    if (g_opt_deterministic || !g_opt_fwd_stream) return false;
+    if (g_opt.deterministic || !g_opt.fwd_stream) return false;
     if (a.pool_key && !(a.mode == 0 && a.n_out[0] == 128)) return false;          // pooled instantiation: 64 -> 128 only
     if (a.n_groups != 1 || a.zin_off[0] != 0 || a.w_off[0] != 0 || a.out_off[0] != 0) return false;
     if (a.n_rows < 32768 || (a.n_out[0] != 64 && a.n_out[0] != 128) || (a.zout && a.zout_pitch != a.n_out[0])) return false;
@@ -1925,21 +1254,9 @@ static bool fwd_streamable(const gad_gemm_fwd_args& a) {
     return (a.Kp == 16 || a.Kp == 8) && a.feat_c == 4 && (a.action ? a.act_c == 6 : a.act_c == 0) && a.feat_c + 3 + a.act_c <= a.Kp;
 }
 
-static Groups make_groups(int n, const int32_t* a, const int32_t* w, const int32_t* o, const int32_t* no) {
-    Groups g;
-    g.n = n;
-    for (int i = 0; i < GAD_MAX_GROUPS; ++i) {
-        g.aoff[i] = (i < n && a) ? a[i] : 0; g.woff[i] = (i < n && w) ? w[i] : 0;
-        g.ooff[i] = (i < n && o) ? o[i] : 0; g.nout[i] = i < n ? no[i] : 0;
-    }
-    return g;
-}
-
-static int max_nout(const Groups& g) { int m = 0; for (int i = 0; i < g.n; ++i) m = g.nout[i] > m ? g.nout[i] : m; return m; }
-
-static int check_input(const gad_gemm_fwd_args& a, const char* who) {
+int check_input(const gad_gemm_fwd_args& a, const char* who) {
     if (a.mode == 2) {
-        GAD_REQUIRE(!g_opt_deterministic, GAD_ERR_UNSUPPORTED, "%s: mode 2 (recomputed 64-channel input) has no deterministic form "
+        GAD_REQUIRE(!g_opt.deterministic, GAD_ERR_UNSUPPORTED, "%s: mode 2 (recomputed 64-channel input) has no deterministic form "
                     "(option \"deterministic\"): store the 64-channel input instead", who);
         GAD_REQUIRE(a.src_xyz && a.row_pt && a.row_grp && a.feat && a.pre_W, GAD_ERR_NULL, "%s: recomputed input needs the gather inputs and pre_W", who);
         GAD_REQUIRE(a.act_c == 0 || a.action, GAD_ERR_NULL, "%s: action", who);
@@ -2005,7 +1322,7 @@ extern "C" int gad_gemm_fwd(const gad_gemm_fwd_args* a, void* stream) {
         GAD_REQUIRE(a->mode != 1 && a->n_groups == 1 && a->zin_off[0] == 0 && a->in_stat_sq && a->in_gamma && a->in_beta && a->scale && a->shift,
                     GAD_ERR_NULL, "gemm_fwd: input-layer BatchNorm block needs an ACT input, one group, in_stat_sq, in_gamma, in_beta, scale, shift");
         const bool has_prologue = fwd_wideable(*a) || (fwd_streamable(*a) && a->mode != 1) || (!pe.key && fwd_skinny(*a));
-        if (!(has_prologue && g_opt_fwd_bn_prologue)) {               // this route reads scale / shift as given: finalise first
+        if (!(has_prologue && g_opt.fwd_bn_prologue)) {               // this route reads scale / shift as given: finalise first
             if (int e = gad_bn_finalize(a->in_stat_sum, a->in_stat_sq, a->in_stat_stride, a->in_gamma, a->in_beta, a->c_in, a->in_count,
                                         a->in_eps, a->in_momentum, a->in_running_mean, a->in_running_var, const_cast<float*>(a->scale),
                                         const_cast<float*>(a->shift), a->in_mean, a->in_istd, stream)) return e;
@@ -2015,12 +1332,8 @@ extern "C" int gad_gemm_fwd(const gad_gemm_fwd_args* a, void* stream) {
     if (!pe.key && fwd_skinny(*a)) {
         // (a NULL zout -- statistics / pooled maxima only -- is honoured by the streaming, wide-tile and 64 x 64 kernels; this one stores unguarded)
         GAD_REQUIRE(a->zout, GAD_ERR_NULL, "gemm_fwd: zout == NULL is not supported for small-M (skinny) shapes");
-        if (g_opt_skinny_nw == 4)
-            hipLaunchKernelGGL(gemm_fwd_skinny_kernel<4>, dim3(gad_cdiv(nmax, 32), gad_cdiv(rows, 32), gr.n), dim3(64 * 4), 0, st, x,
-                               gr, rows, a->row_w, a->W, a->Kp, a->zout, a->zout_pitch, a->stat_sum, a->stat_sq, a->stat_stride, ts);
-        else
-            hipLaunchKernelGGL(gemm_fwd_skinny_kernel<SK_NW>, dim3(gad_cdiv(nmax, 32), gad_cdiv(rows, 32), gr.n), dim3(64 * SK_NW), 0, st, x,
-                               gr, rows, a->row_w, a->W, a->Kp, a->zout, a->zout_pitch, a->stat_sum, a->stat_sq, a->stat_stride, ts);
+        GAD_LAUNCH_SKINNY(gemm_fwd_skinny_kernel, dim3(gad_cdiv(nmax, 32), gad_cdiv(rows, 32), gr.n), st, x, gr, rows, a->row_w, a->W,
+                          a->Kp, a->zout, a->zout_pitch, a->stat_sum, a->stat_sq, a->stat_stride, ts);
         GAD_CHECK_LAUNCH("gemm_fwd(skinny)");
         return GAD_OK;
     }
@@ -2028,7 +1341,7 @@ extern "C" int gad_gemm_fwd(const gad_gemm_fwd_args* a, void* stream) {
     do {                                                                                                   \
         constexpr int BM = WM * TM * 32, BN = WN * TN * 32;                                                \
         int gx = gad_cdiv(grid_rows, BM); if (gx > GAD_GX_CAP) gx = GAD_GX_CAP;                                        \
-        if (g_opt_deterministic && a->stat_sum) {                                                          \
+        if (g_opt.deterministic && a->stat_sum) {                                                          \
             double* slots = det_stat_slots(gx, ncol_stats, stream);                                        \
             if (!slots) return GAD_ERR_LAUNCH;                                                             \
             hipLaunchKernelGGL((gemm_fwd_kernel<WM, WN, TM, TN, XM, POOL, true>), dim3(gx, gad_cdiv(nmax, BN), gr.n), dim3(256), \
@@ -2046,7 +1359,7 @@ extern "C" int gad_gemm_fwd(const gad_gemm_fwd_args* a, void* stream) {
         const int slabs = gad_cdiv(rows, 32);
         // one 8-wavefront workgroup per CU; the gathered first layer (K <= 16: ~100 registers, latency-bound on its five dependent
         // loads per row) may run more (option "fwd_stream_l1_wgs")
-        const int gcap = a->mode == 1 ? g_opt_fwd_stream_l1_wgs : g_opt_fwd_stream_wgs;
+        const int gcap = a->mode == 1 ? g_opt.fwd_stream_l1_wgs : g_opt.fwd_stream_wgs;
         int gx = gad_cdiv(slabs, 8); if (gx > gcap) gx = gcap;
 #define LAUNCH_STREAM(KJ, TN, XM, POOL, ...)                                                               \
         hipLaunchKernelGGL((gemm_fwd_stream_kernel<KJ, TN, XM, POOL, ##__VA_ARGS__>), dim3(gx), dim3(512), 0, st, x, a->n_rows_dev, rows, \
@@ -2097,13 +1410,6 @@ extern "C" int gad_gemm_fwd(const gad_gemm_fwd_args* a, void* stream) {
 // ------------------------------------------------------------------------------------------------
 // backward wrt the layer input:  gout[r][k] = sum_n dZ[r][n] * W[n][k]
 // ------------------------------------------------------------------------------------------------
-struct DxEpi {
-    int mode; float* gout; int gout_pitch; int k_valid;
-    const float* zprev; int zprev_pitch; const float* ps; const float* pt; const float* pm; const float* pi;
-    double* dbeta; double* dgamma; int stat_stride; int store_masked;
-    float* dfeat; int feat_c; const int32_t* row_pt; const int32_t* row_grp; double* daction; int act_c; int gps;
-};
-
 // DET (deterministic mode): e.dbeta / e.dgamma are slot planes of e.stat_stride doubles per block (as in gemm_fwd_kernel)
 template <int WM, int WN, int TM, int TN, bool VEC, int VM, bool DET = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemm_dx_kernel(DzSrc d, Groups gr, const int32_t* __restrict__ n_rows_dev,
@@ -2428,7 +1734,6 @@ __global__ __launch_bounds__(512, 2) void gemm_dx_stream_kernel(DzSrc d, const i
         atomic_add_f64(e.dgamma + (size_t)rep * e.stat_stride + tid, (double)s1);
     }
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // Fused backward of an SA1 layer (rows ~ 2e5, 64 input channels, 64 / 128 output channels): dX AND dW in one pass over
@@ -3309,7 +2614,7 @@ __global__ __launch_bounds__(256) void dx_action_stream_kernel(DzSrc d, const in
 
 // the action-gradient layer: scatter epilogue that wants nothing but daction, G source, 64 channels, 6 action components
 static bool dx_action_streamable(const gad_gemm_dx_args& a, bool vec) {
-    if (g_opt_deterministic || !g_opt_dx_stream || !vec || a.n_groups != 1 || a.dz_off[0] != 0 || a.w_off[0] != 0) return false;
+    if (g_opt.deterministic || !g_opt.dx_stream || !vec || a.n_groups != 1 || a.dz_off[0] != 0 || a.w_off[0] != 0) return false;
     if (a.epilogue != 1 || a.dfeat || !a.daction || a.act_c != 6 || !a.row_grp || a.n_rows < 32768 || a.n_out[0] != 64) return false;
     const gad_dz_src& d = a.dz;
     return d.gmode == 0 && d.G && d.z && d.z_pitch % 4 == 0 && d.g_pitch % 4 == 0 && d.premasked && d.coefP && d.coefQ && d.coefS &&
@@ -3317,11 +2622,11 @@ static bool dx_action_streamable(const gad_gemm_dx_args& a, bool vec) {
 }
 
 static bool dx_wideable(const gad_gemm_dx_args& a, bool vec) {
-    if (g_opt_deterministic || !g_opt_dx_wide || !vec || a.n_groups != 1 || a.dz_off[0] != 0 || a.w_off[0] != 0 || a.gout_off[0] != 0) return false;
+    if (g_opt.deterministic || !g_opt.dx_wide || !vec || a.n_groups != 1 || a.dz_off[0] != 0 || a.w_off[0] != 0 || a.gout_off[0] != 0) return false;
     if (a.n_rows < 2048 || a.k_valid % 128 != 0 || a.k_valid > a.Kp) return false;
     if (a.n_out[0] % 32 != 0 || a.n_out[0] < 32 || a.n_out[0] > 512) return false;
     if (a.epilogue == 1) {                               // scatter into the points' feature gradients (SA2 / SA3 first layers)
-        if (g_opt_dx_wide == 2 || !a.dfeat || a.daction || !a.row_pt || a.k_valid != a.feat_c || a.prev_dbeta) return false;
+        if (g_opt.dx_wide == 2 || !a.dfeat || a.daction || !a.row_pt || a.k_valid != a.feat_c || a.prev_dbeta) return false;
     } else if (!a.prev_dbeta || !a.store_masked || !(a.zprev && a.prev_scale && a.prev_shift && a.prev_mean && a.prev_istd && a.prev_dgamma)) return false;
     const gad_dz_src& d = a.dz;
     if (!d.z || d.z_pitch % 4 != 0 || !d.relu || !d.premasked || !(d.coefP && d.coefQ && d.coefS)) return false;
@@ -3330,7 +2635,7 @@ static bool dx_wideable(const gad_gemm_dx_args& a, bool vec) {
 }
 
 static bool dx_streamable(const gad_gemm_dx_args& a, bool vec) {
-    if (g_opt_deterministic || !g_opt_dx_stream || !vec || a.n_groups != 1 || a.dz_off[0] != 0 || a.w_off[0] != 0 || a.gout_off[0] != 0) return false;
+    if (g_opt.deterministic || !g_opt.dx_stream || !vec || a.n_groups != 1 || a.dz_off[0] != 0 || a.w_off[0] != 0 || a.gout_off[0] != 0) return false;
     if (a.n_rows < 32768 || a.epilogue != 0 || a.k_valid != 64 || a.Kp != 64 || a.gout_pitch != 64) return false;
     if (a.n_out[0] != 64 && a.n_out[0] != 128) return false;
     if (!a.prev_dbeta || a.zprev_pitch != 64 || !a.store_masked) return false;
@@ -3507,7 +2812,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_dx_skinny_kernel(DzSrc d, Groups
 
 // A route whose kernels read P / Q / S per lane (no cooperative prologue) cannot form the BatchNorm-backward coefficients
 // itself: gad_bn_bwd_coef runs first, into the caller's coefP / Q / S scratch, and the block is dropped.
-static int coef_fallback(gad_dz_src& dz, void* stream) {
+int coef_fallback(gad_dz_src& dz, void* stream) {
     if (!dz.bn_dbeta) return GAD_OK;
     GAD_REQUIRE(dz.coefP && dz.coefQ && dz.coefS && dz.scale && dz.bn_dgamma && dz.bn_mean && dz.bn_istd, GAD_ERR_NULL,
                 "BatchNorm-backward block on a route without a prologue needs coefP / Q / S scratch");
@@ -3692,14 +2997,7 @@ extern "C" int gad_gemm_dx(const gad_gemm_dx_args* a, void* stream) {
     if (a->n_rows <= 0) return GAD_OK;
     DzSrc d = make_dzsrc(a->dz);
     Groups gr = make_groups(a->n_groups, a->dz_off, a->w_off, a->gout_off, a->n_out);
-    DxEpi e;
-    e.mode = a->epilogue; e.gout = a->gout; e.gout_pitch = a->gout_pitch; e.k_valid = a->k_valid;
-    e.zprev = a->zprev; e.zprev_pitch = a->zprev_pitch; e.ps = a->prev_scale; e.pt = a->prev_shift;
-    e.pm = a->prev_mean; e.pi = a->prev_istd; e.dbeta = a->prev_dbeta; e.dgamma = a->prev_dgamma;
-    e.stat_stride = a->stat_stride;
-    e.store_masked = (a->store_masked && a->prev_dbeta) ? 1 : 0;
-    e.dfeat = a->dfeat; e.feat_c = a->feat_c; e.row_pt = a->row_pt; e.row_grp = a->row_grp;
-    e.daction = a->daction; e.act_c = a->act_c; e.gps = a->grp_per_sample > 0 ? a->grp_per_sample : 1;
+    DxEpi e = make_dxepi(*a);
     GAD_REQUIRE(e.mode == 0 || (e.row_pt && e.row_grp), GAD_ERR_NULL, "gemm_dx: scatter epilogue needs row maps");
     GAD_REQUIRE(!e.dbeta || (e.zprev && e.ps && e.pt && e.pm && e.pi && e.dgamma), GAD_ERR_NULL, "gemm_dx: prev BN stats inputs");
     hipStream_t st = (hipStream_t)stream;
@@ -3753,14 +3051,9 @@ extern "C" int gad_gemm_dx(const gad_gemm_dx_args* a, void* stream) {
     }
     int nmax_dx = 0;
     for (int i = 0; i < a->n_groups; ++i) nmax_dx = a->n_out[i] > nmax_dx ? a->n_out[i] : nmax_dx;
-    if (!g_opt_deterministic && g_opt_dx_skinny && vec && e.mode == 0 && a->dz.gmode == 0 && !a->n_rows_dev && rows <= 1024 &&
+    if (!g_opt.deterministic && g_opt.dx_skinny && vec && e.mode == 0 && a->dz.gmode == 0 && !a->n_rows_dev && rows <= 1024 &&
         nmax_dx <= VMAX) {
-        if (g_opt_skinny_nw == 4)
-            hipLaunchKernelGGL(gemm_dx_skinny_kernel<4>, dim3(gad_cdiv(kv, 32), gad_cdiv(rows, 32), gr.n), dim3(64 * 4), 0, st, d, gr,
-                               rows, a->W, a->Kp, e, ts);
-        else
-            hipLaunchKernelGGL(gemm_dx_skinny_kernel<SK_NW>, dim3(gad_cdiv(kv, 32), gad_cdiv(rows, 32), gr.n), dim3(64 * SK_NW), 0, st, d, gr,
-                               rows, a->W, a->Kp, e, ts);
+        GAD_LAUNCH_SKINNY(gemm_dx_skinny_kernel, dim3(gad_cdiv(kv, 32), gad_cdiv(rows, 32), gr.n), st, d, gr, rows, a->W, a->Kp, e, ts);
         GAD_CHECK_LAUNCH("gemm_dx(skinny)");
         return GAD_OK;
     }
@@ -3768,7 +3061,7 @@ extern "C" int gad_gemm_dx(const gad_gemm_dx_args* a, void* stream) {
     do {                                                                                                 \
         constexpr int BM = WM * TM * 32, BN = WN * TN * 32;                                              \
         int gx = gad_cdiv(grid_rows, BM); if (gx > GAD_GX_CAP) gx = GAD_GX_CAP;                                      \
-        if (g_opt_deterministic) {                                                                       \
+        if (g_opt.deterministic) {                                                                       \
             if (int e_ = det_dx_launch<WM, WN, TM, TN, V>(a, d, gr, e, gx, nmax_dx, ts, stream)) return e_; \
             return GAD_OK;                                                                               \
         }                                                                                                \
@@ -3786,1155 +3079,6 @@ extern "C" int gad_gemm_dx(const gad_gemm_dx_args* a, void* stream) {
 #undef LAUNCH_DX
 #undef LAUNCH_DX2
     GAD_CHECK_LAUNCH("gemm_dx");
-    return GAD_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// backward wrt the weights:  gacc[n][k] += sum_r dZ[r][n] * X[r][k]
-// split over rows: every (tile, split) block writes its partial tile to the caller's workspace, a
-// second kernel sums the splits in f64.  Without a workspace: f64 atomics.
-// ------------------------------------------------------------------------------------------------
-// VM: stride of the per-channel vectors in LDS (>= the widest layer side).  512 instead of VMAX = 1024 brings the
-// workgroup from 46 KB to 32 KB of LDS: four instead of three resident workgroups per CU (the register budget allows four).
-template <int WM, int WN, int TM, int TN, int XM, bool VEC, int VM>
-__global__ __launch_bounds__(256) void gemm_dw_kernel(DzSrc d, XSrc x, Groups gr,
-                                                       const int32_t* __restrict__ n_rows_dev, int n_rows_static,
-                                                       int Kp, int k_used, int n_ktiles, double* __restrict__ gacc,
-                                                       float* __restrict__ partial, long long group_stride, unsigned long long* __restrict__ ts) {
-    KTimer kt(ts);
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    constexpr int PA = PitchD<BM>::v, PB = PitchD<BN>::v;
-    constexpr int UA = BM * 8 / 256, UB = BN * 8 / 256;
-    constexpr int TILE = KT * PA + KT * PB;
-    constexpr int SM = TILE + (VEC ? 5 * VM : 4) + 2 * VM;
-    __shared__ __attribute__((aligned(16))) float smem[SM];
-    float* As = smem;
-    float* Bs = smem + KT * PA;
-    float* vec = smem + TILE;
-    float* sv = vec + (VEC ? 5 * VM : 4);
-    float* tv = sv + VM;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int g = blockIdx.z;
-    const int doff = gr.aoff[g], zoff = gr.ooff[g], n_out = gr.nout[g];
-    const int tile_n = blockIdx.x / n_ktiles, tile_k = blockIdx.x % n_ktiles;
-    const int n0 = tile_n * BM, k0 = tile_k * BN;
-    if (n0 >= n_out) return;
-    const int n_rows = n_rows_dev ? min(*n_rows_dev, n_rows_static) : n_rows_static;
-    int chunk = gad_cdiv_dev(n_rows, (int)gridDim.y);
-    chunk = (chunk + KT - 1) / KT * KT;
-    const int r_begin = blockIdx.y * chunk;
-    const int r_end = min(r_begin + chunk, n_rows);
-    if (r_begin >= r_end) return;     // the reducer skips the same splits (same chunk arithmetic)
-    if (VEC) stage_dz_vecs<VM>(vec, d, doff, n_out);
-    if (XM == 0 && x.affine) stage_affine<256>(sv, tv, x, zoff, x.c_in);
-    __syncthreads();
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
-    DzRaw ra[UA];
-    float wa[UA];
-    XRaw rb[UB];
-    const int bulk = XM == 0 ? x.c_in : x.feat_c;
-    const bool tail = k0 + BN > bulk;
-    // row -> group / point indices are needed to ADDRESS the pooled-gradient and gather loads: fetched one K-tile
-    // ahead of the data they address, so a tile's load phase is one memory latency, not two chained ones
-    int gq[UA], pq[UB], xq[UB];
-    auto load_idx = [&](int rb0) {
-#pragma unroll
-        for (int it = 0; it < UA; ++it) {
-            int kk, i; unit_D<BM>(it * 256 + tid, kk, i);
-            const int r = rb0 + kk;
-            gq[it] = d.gmode != 0 ? d.row_grp[r < r_end ? r : 0] : 0;
-        }
-#pragma unroll
-        for (int it = 0; it < UB; ++it) {
-            int kk, j; unit_D<BN>(it * 256 + tid, kk, j);
-            const int r = rb0 + kk;
-            const int rr = r < r_end ? r : 0;
-            pq[it] = XM == 1 ? x.row_pt[rr] : 0;
-            xq[it] = (XM == 1 && tail) ? x.row_grp[rr] : -1;
-        }
-    };
-    auto load_tile = [&](int rb0) {
-#pragma unroll
-        for (int it = 0; it < UA; ++it) {
-            int kk, i; unit_D<BM>(it * 256 + tid, kk, i);
-            const int r = rb0 + kk;
-            const bool ok = r < r_end;
-            const int rr = ok ? r : 0;
-            wa[it] = d.row_w ? d.row_w[rr] : 1.f;
-            ra[it] = dz_raw<VEC>(d, r, ok, doff, n0 + i, n_out, gq[it]);
-        }
-#pragma unroll
-        for (int it = 0; it < UB; ++it) {
-            int kk, j; unit_D<BN>(it * 256 + tid, kk, j);
-            const int r = rb0 + kk;
-            const bool ok = r < r_end && (k0 + j < Kp);
-            rb[it] = x_raw<XM>(x, r, ok, zoff, k0 + j, tail, pq[it], xq[it]);
-        }
-        load_idx(rb0 + KT);
-    };
-    auto store_tile = [&](int rb0) {
-#pragma unroll
-        for (int it = 0; it < UA; ++it) {
-            int kk, i; unit_D<BM>(it * 256 + tid, kk, i);
-            const int r = rb0 + kk;
-            store_D<BM>(As, kk, i, dz_finish<VEC, VM>(d, ra[it], r, r < r_end, n0 + i, n_out, wa[it], vec));
-        }
-#pragma unroll
-        for (int it = 0; it < UB; ++it) {
-            int kk, j; unit_D<BN>(it * 256 + tid, kk, j);
-            const int r = rb0 + kk;
-            const bool ok = r < r_end && (k0 + j < Kp);
-            store_D<BN>(Bs, kk, j, x_finish<XM>(x, rb[it], ok, k0 + j, sv, tv));
-        }
-    };
-    load_idx(r_begin);
-    load_tile(r_begin);
-    for (int rb0 = r_begin; rb0 < r_end; rb0 += KT) {
-        store_tile(rb0);
-        __syncthreads();
-        if (rb0 + KT < r_end) load_tile(rb0 + KT);
-        mfma_ktile<TM, TN, PA, PB>(As, Bs, wm * TM * 32, wn * TN * 32, lane, acc);
-        __syncthreads();
-    }
-    const int l31 = lane & 31, half = lane >> 5;
-    float* pout = partial ? partial + (size_t)g * group_stride + (size_t)blockIdx.y * n_out * Kp : nullptr;
-    double* aout = gacc + gr.woff[g];
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-        const int k = k0 + wn * TN * 32 + tn * 32 + l31;
-        if (k >= k_used) continue;
-#pragma unroll
-        for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int n = n0 + wm * TM * 32 + tm * 32 + acc_row(v, half);
-                if (n >= n_out) continue;
-                if (pout) pout[(size_t)n * Kp + k] = acc[tm][tn][v];
-                else atomic_add_f64(aout + (size_t)n * Kp + k, (double)acc[tm][tn][v]);
-            }
-    }
-}
-
-#define DW_RED_CHUNK 16
-// all_active: every split wrote its partial tile (the streaming kernels deal row units to the splits round-robin); else the
-// splits are contiguous row chunks and those past the live rows were not written
-__global__ __launch_bounds__(256) void dw_reduce_kernel(const float* __restrict__ partial, long long group_stride,
-                                                        Groups gr, const int32_t* __restrict__ n_rows_dev,
-                                                        int n_rows_static, int splits, int Kp, int k_used,
-                                                        double* __restrict__ gacc, int all_active = 0) {
-    const int g = blockIdx.z;
-    const int n_out = gr.nout[g];
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (long long)n_out * Kp) return;
-    const int k = (int)(e % Kp);
-    if (k >= k_used) return;
-    const int n_rows = n_rows_dev ? min(*n_rows_dev, n_rows_static) : n_rows_static;
-    int chunk = (n_rows + splits - 1) / splits;
-    chunk = (chunk + KT - 1) / KT * KT;
-    const int active = all_active ? splits : (chunk > 0 ? (n_rows + chunk - 1) / chunk : 0);
-    const int s0 = blockIdx.y * DW_RED_CHUNK, s1 = min(s0 + DW_RED_CHUNK, active);
-    if (s0 >= s1) return;
-    const float* p = partial + (size_t)g * group_stride + e;
-    const size_t stride = (size_t)n_out * Kp;
-    double s = 0.0;
-#pragma unroll 4
-    for (int sidx = s0; sidx < s1; ++sidx) s += (double)p[(size_t)sidx * stride];
-    atomic_add_f64(gacc + gr.woff[g] + e, s);
-}
-
-// skinny dW for the small-M layers (FC head, actor / critic heads: <= 1024 rows to reduce over, outputs up to 1024 x 1032).
-// One 32x32 tile of dW per workgroup, the 8 wavefronts split the ROWS.  Both MFMA operands are indexed [row][channel]
-// in memory with the reduction index (rows) leading, so with the k = 8j+4h+i visiting order lane (channel = lane%32)
-// needs four consecutive rows of its channel: four coalesced 4-byte loads each for z, dY (-> dZ in registers, per-lane
-// BatchNorm constants) and for the layer input (-> act(scale*z+shift), or the bias / extra column).  No LDS staging,
-// all loads of a wavefront's rows in flight before its first MFMA; partial tiles summed through LDS, then f64 atomics
-// straight into the gradient arena (no split-K workspace, no reduce launch).
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void gemm_dw_skinny_kernel(DzSrc d, XSrc x, Groups gr, int n_rows, int Kp,
-                                                                    int k_used, double* __restrict__ gacc, unsigned long long* __restrict__ ts) {
-    KTimer kt(ts);
-    __shared__ float part[NW * 16 * 64];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, half = lane >> 5;
-    const int g = blockIdx.z;
-    const int doff = gr.aoff[g], zoff = gr.ooff[g], n_out = gr.nout[g];
-    const int n0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
-    if (n0 >= n_out) return;
-    // A side: this lane's output channel n and its BatchNorm-backward constants
-    const int n = n0 + l31;
-    const bool n_ok = n < n_out;
-    const int ch = doff + (n_ok ? n : 0);
-    const float dsc = (d.scale && !d.premasked) ? d.scale[ch] : 1.f, dsh = (d.scale && !d.premasked) ? d.shift[ch] : 0.f;
-    float dP, dQ, dS;
-    dz_coef(d, ch, dP, dQ, dS);
-    // B side: this lane's input column k: 0 = activation column, 1 = extra column, 2 = bias (ones) column, 3 = padding
-    const int k = k0 + l31;
-    const int kind = k < x.c_in ? 0 : ((k == x.c_in && x.extra) ? 1 : (k == x.ones_col ? 2 : 3));
-    const int kc = zoff + (kind == 0 ? k : 0);
-    const float xs = (kind == 0 && x.scale) ? x.scale[kc] : 1.f, xt = (kind == 0 && x.shift) ? x.shift[kc] : 0.f;
-
-    const int units = (n_rows + 7) >> 3;
-    const int per = (units + NW - 1) / NW;
-    const int u0 = wave * per, u1 = min(units, u0 + per);
-    f32x16 acc;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-    constexpr int CHU = 4;                                   // 8-row units per register chunk
-    for (int c0 = u0; c0 < u1; c0 += CHU) {
-        float rz[CHU][4], rg[CHU][4], rx[CHU][4], rw[CHU][4];
-#pragma unroll
-        for (int u = 0; u < CHU; ++u)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = 8 * (c0 + u) + 4 * half + i;
-                const int rr = min(r, max(n_rows - 1, 0));
-                rz[u][i] = d.z ? d.z[(size_t)rr * d.z_pitch + ch] : 0.f;
-                rg[u][i] = d.G[(size_t)rr * d.g_pitch + ch];
-                rw[u][i] = d.row_w ? d.row_w[rr] : 1.f;
-                rx[u][i] = kind == 0 ? x.zin[(size_t)rr * x.zin_pitch + kc] : (kind == 1 ? x.extra[rr] : (kind == 2 ? 1.f : 0.f));
-            }
-#pragma unroll
-        for (int u = 0; u < CHU; ++u) {
-            if (c0 + u >= u1) break;                         // wave-uniform
-            float a4[4], b4[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = 8 * (c0 + u) + 4 * half + i;
-                const bool live = r < n_rows;
-                const float z = rz[u][i];
-                float gq = rg[u][i];
-                if (d.relu && !d.premasked) gq = fmaf(z, dsc, dsh) > 0.f ? gq : 0.f;
-                if (d.coef) gq = dP * gq - rw[u][i] * fmaf(dS, z, dQ);
-                a4[i] = (live && n_ok) ? gq : 0.f;
-                float xv = rx[u][i];
-                if (kind == 0) { xv = fmaf(xv, xs, xt); if (x.relu) xv = fmaxf(xv, 0.f); }
-                b4[i] = live ? xv : 0.f;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[i], b4[i], acc, 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int v = 0; v < 16; ++v) part[(wave * 16 + v) * 64 + lane] = acc[v];
-    __syncthreads();
-    if (wave != 0) return;
-#pragma unroll
-    for (int w = 1; w < NW; ++w)
-#pragma unroll
-        for (int v = 0; v < 16; ++v) acc[v] += part[(w * 16 + v) * 64 + lane];
-    if (k >= k_used) return;
-    double* aout = gacc + gr.woff[g];
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int nn = n0 + acc_row(v, half);
-        if (nn < n_out) atomic_add_f64(aout + (size_t)nn * Kp + k, (double)acc[v]);
-    }
-}
-
-// Streaming dW for the SA1 layers (>= 32k de-duplicated rows, 64 input channels, 64 or 128 output channels).
-// dW[n][k] = sum_r dZ[r][n] * X[r][k]: the reduction index is the leading index of both operands in memory, so a lane that
-// owns output channel n (A side) / input channel k (B side) feeds the MFMA straight from coalesced 4-byte global loads --
-// no LDS tiles, no barriers in the loop, BatchNorm constants per lane in registers (as in the skinny kernel above).
-// Work split: a workgroup of 8 wavefronts owns one split of the rows (the dw_reduce geometry: blockIdx.x = split);
-// for 128 output channels wavefronts 0-3 take output channels 0-63 and 4-7 take 64-127, each set dealing the split's
-// 8-row units among its four members.  Every wavefront keeps a 64 x 64 block of dW in 64 accumulator registers
-// (2 x 2 MFMA tiles: each loaded operand is used twice), loads unit u+1 while computing unit u, and the four partial
-// blocks are summed through LDS into the split's partial tile.
-template <int NG, int GM>
-__global__ __launch_bounds__(512) void gemm_dw_stream_kernel(DzSrc d, XSrc x, const int32_t* __restrict__ n_rows_dev,
-                                                             int n_rows_static, int splits, float* __restrict__ partial, unsigned long long* __restrict__ ts) {
-    KTimer kt(ts);
-    constexpr int NO = 64 * NG, KP = 64, RW = 8 / NG;              // RW: wavefronts that share the rows of one column set
-    __shared__ float red[8 * 16 * 64];                             // one accumulator tile of every wavefront
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, half = lane >> 5;
-    const int cset = wave / RW, wr = wave % RW;                    // column set, rank among the wavefronts of that set
-    const int n_rows = n_rows_dev ? min(*n_rows_dev, n_rows_static) : n_rows_static;
-    // 8-row units are dealt to the workgroups ROUND-ROBIN (unit = (k * gridDim.x + blockIdx.x) * RW + rank): at any time
-    // the whole grid reads one contiguous window of rows and that window sweeps the arrays front to back -- the order in
-    // which the dX kernel of the same layer, running beside this one on the main stream, walks them too, so the second
-    // reader of z / dY finds the lines in the L2 / Infinity Cache instead of HBM (contiguous chunks per workgroup touched
-    // all of the array at once).  Every workgroup writes its partial tile (zeros without rows): dw_reduce all_active.
-    const int r_begin = 0, r_end = n_rows;
-    (void)splits;
-
-    // per-lane constants: A side (dZ) output channels n = 64 cset + 32 j + l31, B side (X) input channels k = 32 b + l31
-    float dP[2], dQ[2], dS[2], xs[2], xt[2];          // (the ReLU mask is already in dY: premasked)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int ch = 64 * cset + 32 * j + l31;
-        dz_coef(d, ch, dP[j], dQ[j], dS[j]);
-        xs[j] = x.scale[32 * j + l31]; xt[j] = x.shift[32 * j + l31];
-    }
-    // Addressing of the main loop: raw buffer loads whose per-lane byte offset is a CONSTANT (channel block + the
-    // half-wave's 4-row stagger) and whose row position lives in the scalar offset -- no vector ALU work per load.
-    const unsigned lane_n = 64u * cset + l31;
-    const int zpitch4 = d.z_pitch * 4, xpitch4 = x.zin_pitch * 4, gpitch4 = (GM == 0 ? d.g_pitch : d.c) * 4;
-    const __amdgpu_buffer_rsrc_t zr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.z), 0, GAD_BUF_MAX, 0x00020000);
-    const __amdgpu_buffer_rsrc_t gr_ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(GM == 0 ? d.G : d.dout), 0, GAD_BUF_MAX, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(GM == 0 ? d.row_grp : d.argmax), 0, GAD_BUF_MAX, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x.zin), 0, GAD_BUF_MAX, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr_ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.row_w ? d.row_w : d.z), 0, GAD_BUF_MAX, 0x00020000);
-    const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(GM == 0 ? d.argmax : d.row_grp), 0, GAD_BUF_MAX, 0x00020000);
-    const int vl_z = 4 * half * zpitch4 + (int)lane_n * 4, vl_x = 4 * half * xpitch4 + l31 * 4;
-    const int vl_g = (GM == 0 ? 4 * half * gpitch4 : 0) + (int)lane_n * 4, vl_r = 4 * half * 4;
-
-    struct Unit { float z[4][2], g[4][2], xv[4][2], w[4]; int a[4][2]; };
-    auto ldf = [](__amdgpu_buffer_rsrc_t r, int vo, int so) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0)); };
-    auto load = [&](Unit& u, int unit) {                           // a unit with all eight rows inside the split
-        const int rs = r_begin + 8 * unit;                         // scalar
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            u.w[i] = d.row_w ? ldf(wr_, vl_r, (rs + i) * 4) : 1.f;
-            int vg = vl_g;
-            if (GM == 1) vg = (int)__builtin_amdgcn_raw_buffer_load_b32(pr, vl_r, (rs + i) * 4, 0) * gpitch4 + vl_g;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                u.z[i][j] = ldf(zr, vl_z + 128 * j, (rs + i) * zpitch4);
-                u.g[i][j] = ldf(gr_, vg + 128 * j, GM == 0 ? (rs + i) * gpitch4 : 0);
-                if (GM == 1) u.a[i][j] = (int)__builtin_amdgcn_raw_buffer_load_b32(ar, vg + 128 * j, 0, 0);
-                u.xv[i][j] = ldf(xr, vl_x + 128 * j, (rs + i) * xpitch4);
-            }
-        }
-    };
-    auto load_tail = [&](Unit& u, int unit) {                      // the ragged last unit: clamped rows, plain loads
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = min(r_begin + 8 * unit + 4 * half + i, r_end - 1);
-            u.w[i] = d.row_w ? d.row_w[r] : 1.f;
-            const size_t go = (GM == 0 ? (size_t)r * d.g_pitch : (size_t)d.row_grp[r] * d.c) + lane_n;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                u.z[i][j] = d.z[(size_t)r * d.z_pitch + lane_n + 32 * j];
-                u.g[i][j] = (GM == 0 ? d.G : d.dout)[go + 32 * j];
-                if (GM == 1) u.a[i][j] = d.argmax[go + 32 * j];
-                u.xv[i][j] = x.zin[(size_t)r * x.zin_pitch + l31 + 32 * j];
-            }
-        }
-    };
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[j][b][v] = 0.f;
-    auto compute = [&](const Unit& u, int unit, auto tail) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = r_begin + 8 * unit + 4 * half + i;
-            const bool live = !decltype(tail)::value || r < r_end;
-            float a2[2], b2[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float z = u.z[i][j];
-                float gq = u.g[i][j];
-                if (GM == 1) gq = u.a[i][j] == r ? gq : 0.f;
-                gq = dP[j] * gq - u.w[i] * fmaf(dS[j], z, dQ[j]);
-                a2[j] = live ? gq : 0.f;
-                const float xv = fmaxf(fmaf(u.xv[i][j], xs[j], xt[j]), 0.f);
-                b2[j] = live ? xv : 0.f;
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) acc[j][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[j], b2[b], acc[j][b], 0, 0, 0);
-        }
-    };
-    const std::integral_constant<bool, false> full;
-    const std::integral_constant<bool, true> part;
-    const int nfull = (r_end - r_begin) >> 3;                      // units with all eight rows live
-    const int ustep = gridDim.x * RW;
-    Unit u0, u1;
-    int un = blockIdx.x * RW + wr;
-    if (un < nfull) load(u0, un);
-    while (un < nfull) {
-        if (un + ustep < nfull) load(u1, un + ustep);
-        compute(u0, un, full);
-        un += ustep;
-        if (un >= nfull) break;
-        if (un + ustep < nfull) load(u0, un + ustep);
-        compute(u1, un, full);
-        un += ustep;
-    }
-    if (((r_end - r_begin) & 7) != 0 && (nfull / RW) % gridDim.x == blockIdx.x && wr == nfull % RW) {   // the ragged last unit
-        load_tail(u0, nfull);
-        compute(u0, nfull, part);
-    }
-    // the set's RW partial 64 x 64 blocks -> one: tile (j, b) of every wavefront through LDS, summed by wavefront (j, b) of the set
-    float* pout = partial + (size_t)blockIdx.x * NO * KP;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int j = t >> 1, b = t & 1;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) red[(wave * 16 + v) * 64 + lane] = acc[j][b][v];
-        __syncthreads();
-        if (wr == t % RW) {
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                float sum = 0.f;
-#pragma unroll
-                for (int w = 0; w < RW; ++w) sum += red[((cset * RW + w) * 16 + v) * 64 + lane];
-                const int n = 64 * cset + 32 * j + acc_row(v, half), k = 32 * b + l31;
-                pout[(size_t)n * KP + k] = sum;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// Streaming dW for SA1 layer 1, whose input rows are GATHERED: [feat[pt] | src_xyz[pt] - ctr_xyz[grp] | action[sample] | 0]
-// (<= 32 columns, no BatchNorm in front).  Same scheme as above with one B tile: lane c of the B side produces input column
-// c of its rows from per-lane constants (which array, which stride, which component), the A side is the adjacent-pair
-// mapping (accumulator row i of tile j = output channel 2 i + j, one 8-byte load per row for z and for dY).
-__global__ __launch_bounds__(512) void gemm_dw_gather_stream_kernel(DzSrc d, XSrc x, const int32_t* __restrict__ n_rows_dev,
-                                                                    int n_rows_static, int splits, int Kp, int k_used,
-                                                                    float inv_gps, float* __restrict__ partial, unsigned long long* __restrict__ ts) {
-    KTimer kt(ts);
-    constexpr int RW = 8;
-    typedef unsigned gad_u32x2 __attribute__((ext_vector_type(2)));
-    __shared__ float red[8 * 16 * 64];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, half = lane >> 5;
-    const int n_rows = n_rows_dev ? min(*n_rows_dev, n_rows_static) : n_rows_static;
-    const int r_begin = 0, r_end = n_rows;         // units dealt round-robin over the grid (see gemm_dw_stream_kernel)
-    (void)splits;
-
-    const unsigned lane_n = 2u * l31;
-    float dP[2], dQ[2], dS[2];                        // (premasked dY)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) dz_coef(d, lane_n + j, dP[j], dQ[j], dS[j]);
-    // B side: what input column k = l31 is made of
-    const int k = l31, fc = x.feat_c;
-    const int kind = k < fc ? 0 : (k < fc + 3 ? 1 : ((x.action && k < fc + 3 + x.act_c) ? 2 : 3));
-    const float* base1 = kind == 0 ? x.feat : (kind == 1 ? x.src_xyz : (kind == 2 ? x.action : x.feat));
-    const int stride1 = kind == 0 ? fc : (kind == 1 ? 3 : (kind == 2 ? x.act_c : 0));
-    const int off1 = kind == 0 ? k : (kind == 1 ? k - fc : (kind == 2 ? k - fc - 3 : 0));
-    const bool sub_ctr = kind == 1 && x.ctr_xyz != nullptr;
-    const float* base2 = sub_ctr ? x.ctr_xyz + off1 : x.src_xyz;   // lanes without a centre read a valid address, unused
-
-    const int zpitch4 = d.z_pitch * 4, gpitch4 = d.g_pitch * 4;
-    const __amdgpu_buffer_rsrc_t zr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.z), 0, GAD_BUF_MAX, 0x00020000);
-    const __amdgpu_buffer_rsrc_t gr_ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.G), 0, GAD_BUF_MAX, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr_ = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.row_w ? d.row_w : d.z), 0, GAD_BUF_MAX, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ptr_ = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(x.row_pt), 0, GAD_BUF_MAX, 0x00020000);
-    const __amdgpu_buffer_rsrc_t grpr = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(x.row_grp), 0, GAD_BUF_MAX, 0x00020000);
-    const int vl_z = 4 * half * zpitch4 + (int)lane_n * 4, vl_g = 4 * half * gpitch4 + (int)lane_n * 4, vl_r = 4 * half * 4;
-
-    struct Unit { float z[4][2], g[4][2], w[4], x1[4], x2[4]; };
-    auto gather = [&](Unit& u, int i, int pt, int grp) {
-        int idx = pt;
-        if (kind == 2) {                                           // sample = grp / gps (gps need not be a power of two)
-            int q = (int)((float)grp * inv_gps);
-            const int rem = grp - q * x.gps;
-            q += rem >= x.gps ? 1 : (rem < 0 ? -1 : 0);
-            idx = q;
-        }
-        u.x1[i] = base1[(size_t)idx * stride1 + off1];
-        u.x2[i] = base2[sub_ctr ? (size_t)grp * 3 : 0];
-    };
-    auto load = [&](Unit& u, int unit) {
-        const int rs = r_begin + 8 * unit;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int pt = (int)__builtin_amdgcn_raw_buffer_load_b32(ptr_, vl_r, (rs + i) * 4, 0);
-            const int grp = (int)__builtin_amdgcn_raw_buffer_load_b32(grpr, vl_r, (rs + i) * 4, 0);
-            u.w[i] = d.row_w ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(wr_, vl_r, (rs + i) * 4, 0)) : 1.f;
-            const gad_u32x2 zz = __builtin_amdgcn_raw_buffer_load_b64(zr, vl_z, (rs + i) * zpitch4, 0);
-            const gad_u32x2 gg = __builtin_amdgcn_raw_buffer_load_b64(gr_, vl_g, (rs + i) * gpitch4, 0);
-            u.z[i][0] = __uint_as_float(zz.x); u.z[i][1] = __uint_as_float(zz.y);
-            u.g[i][0] = __uint_as_float(gg.x); u.g[i][1] = __uint_as_float(gg.y);
-            gather(u, i, pt, grp);
-        }
-    };
-    auto load_tail = [&](Unit& u, int unit) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = min(r_begin + 8 * unit + 4 * half + i, r_end - 1);
-            u.w[i] = d.row_w ? d.row_w[r] : 1.f;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                u.z[i][j] = d.z[(size_t)r * d.z_pitch + lane_n + j];
-                u.g[i][j] = d.G[(size_t)r * d.g_pitch + lane_n + j];
-            }
-            gather(u, i, x.row_pt[r], x.row_grp[r]);
-        }
-    };
-    f32x16 acc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int v = 0; v < 16; ++v) acc[j][v] = 0.f;
-    auto compute = [&](const Unit& u, int unit, auto tail) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = r_begin + 8 * unit + 4 * half + i;
-            const bool live = !decltype(tail)::value || r < r_end;
-            float xv = sub_ctr ? __fsub_rn(u.x1[i], u.x2[i]) : u.x1[i];
-            xv = (kind != 3 && live) ? xv : 0.f;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float z = u.z[i][j];
-                const float gq = dP[j] * u.g[i][j] - u.w[i] * fmaf(dS[j], z, dQ[j]);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(live ? gq : 0.f, xv, acc[j], 0, 0, 0);
-            }
-        }
-    };
-    const std::integral_constant<bool, false> full;
-    const std::integral_constant<bool, true> part;
-    const int nfull = (r_end - r_begin) >> 3;
-    const int ustep = gridDim.x * RW;
-    Unit u0, u1;
-    int un = blockIdx.x * RW + wave;
-    if (un < nfull) load(u0, un);
-    while (un < nfull) {
-        if (un + ustep < nfull) load(u1, un + ustep);
-        compute(u0, un, full);
-        un += ustep;
-        if (un >= nfull) break;
-        if (un + ustep < nfull) load(u0, un + ustep);
-        compute(u1, un, full);
-        un += ustep;
-    }
-    if (((r_end - r_begin) & 7) != 0 && (nfull / RW) % gridDim.x == blockIdx.x && wave == nfull % RW) {
-        load_tail(u0, nfull);
-        compute(u0, nfull, part);
-    }
-    float* pout = partial + (size_t)blockIdx.x * 64 * Kp;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-#pragma unroll
-        for (int v = 0; v < 16; ++v) red[(wave * 16 + v) * 64 + lane] = acc[j][v];
-        __syncthreads();
-        if ((wave >> 2) == j) {                                    // four wavefronts per tile, four accumulator rows each
-#pragma unroll
-            for (int vv = 0; vv < 4; ++vv) {
-                const int v = 4 * (wave & 3) + vv;
-                float sum = 0.f;
-#pragma unroll
-                for (int w = 0; w < RW; ++w) sum += red[(w * 16 + v) * 64 + lane];
-                const int n = 2 * acc_row(v, half) + j;
-                if (l31 < Kp) pout[(size_t)n * Kp + l31] = l31 < k_used ? sum : 0.f;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// wide-tile dW for the MID-SIZE layers: dW[n][k] = sum_r dZ[r][n] * X[r][k] is a tiny output (128 x 128 ... 512 x 256)
-// behind a long reduction (8e3 - 3e4 rows).  The 64 x 64 kernel re-reads every row of dZ and X once per output tile (4 - 32
-// times through L2: 112 MB of traffic for 42 MB of operands) and keeps one accumulator per wavefront.  Here a workgroup owns
-// a 128 x 128 block of dW for its chunk of rows -- the whole matrix for the 128-wide layers -- a wavefront 64 x 64 (four
-// accumulators: each staged operand value feeds two MFMAs), K-tile = 32 rows, LDS double-buffered with one barrier per
-// K-tile, operands stored as loaded ([row][128 + 4]: one ds_write_b128 per staged float4, fragments are conflict-free
-// ds_read_b32 of consecutive channels).  dZ = P*dY - w*(Q + S*z) and X = relu(scale*z_in + shift) are formed once per
-// staged element.  Partial tiles go to the caller's workspace, dw_reduce sums the row chunks in f64.
-// XM = 1 (first layer of SA2 / SA3: gathered input [feat[pt] | src_xyz[pt] - ctr_xyz[grp]]): the X side is feat[pt] as
-// stored (row -> point indices fetched one K-tile ahead of the rows they address); the three coordinate columns of dW are
-// sums of dZ * dx accumulated with vector FMAs while dZ is staged (12 per float4) by the workgroups of the first k block.
-// ------------------------------------------------------------------------------------------------
-template <int XM, int GM>
-__global__ __launch_bounds__(256, 2) void gemm_dw_wide_kernel(DzSrc d, XSrc x, const int32_t* __restrict__ n_rows_dev,
-                                                              int n_rows_static, int Kp, int n_out, int tiles_k,
-                                                              float* __restrict__ partial, unsigned long long* __restrict__ ts) {
-    KTimer kt_(ts);
-    constexpr int BT = 128, P = BT + 4, STAGE = 2 * KT * P, VM = 512;
-    __shared__ __attribute__((aligned(16))) float smem[2 * STAGE + 5 * VM];
-    float* vP = smem + 2 * STAGE;                        // P | Q | S of the dZ channels, scale | shift of the input channels
-    float* sv = vP + 3 * VM;
-    float* tv = sv + VM;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int l31 = lane & 31, half = lane >> 5;
-    const int n0 = (blockIdx.x / tiles_k) * BT, k0 = (blockIdx.x % tiles_k) * BT;
-    const int n_rows = n_rows_dev ? min(*n_rows_dev, n_rows_static) : n_rows_static;
-    int chunk = gad_cdiv_dev(n_rows, (int)gridDim.y);
-    chunk = (chunk + KT - 1) / KT * KT;                  // == dw_reduce_kernel's split geometry
-    const int r_begin = blockIdx.y * chunk, r_end = min(r_begin + chunk, n_rows);
-    if (r_begin >= r_end) return;                        // the reducer skips the same splits
-    for (int i = tid; i < BT; i += 256) {
-        float Pc, Qc, Sc;
-        dz_coef(d, n0 + i, Pc, Qc, Sc, blockIdx.y == 0 && k0 == 0);
-        vP[i] = Pc; vP[VM + i] = Qc; vP[2 * VM + i] = Sc;
-        if (XM == 0) { sv[i] = x.scale[k0 + i]; tv[i] = x.shift[k0 + i]; }
-    }
-    const bool coords = XM == 1 && k0 == 0;              // this workgroup also forms dW[n][feat_c .. feat_c + 2]
-    float wx[4][3];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { wx[j][0] = 0.f; wx[j][1] = 0.f; wx[j][2] = 0.f; }
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.f;
-    // staging: a K-tile is 32 rows x 128 channels per side = 1024 float4: thread -> rows sr + 8 u (u < 4), channels c4 .. c4 + 3
-    const int c4 = (tid & 31) * 4, sr = tid >> 5;
-    const int gpitch = GM == 0 ? d.g_pitch : d.c;
-    float4 rz[4], rg[4], rx[4];
-    int4 ra[4];
-    float rw[4], rd[4][3];
-    int pq[4], gq[4];                                    // XM = 1: point / group of the NEXT tile's rows
-    int gd[4];                                           // GM = 1: group of the NEXT tile's rows (pooled gradient source)
-    auto load_idx = [&](int rb0) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int r = rb0 + sr + 8 * u;
-            const int rr = r < r_end ? r : r_end - 1;
-            pq[u] = XM == 1 ? x.row_pt[rr] : 0;
-            gq[u] = (XM == 1 && x.ctr_xyz) ? x.row_grp[rr] : 0;
-            gd[u] = GM == 1 ? d.row_grp[rr] : 0;
-        }
-    };
-    auto load_regs = [&](int rb0) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int r = rb0 + sr + 8 * u;
-            const int rr = r < r_end ? r : r_end - 1;
-            rw[u] = d.row_w ? d.row_w[rr] : 1.f;
-            rz[u] = ldg4(d.z + (size_t)rr * d.z_pitch + n0 + c4);
-            if (GM == 0) {
-                rg[u] = ldg4(d.G + (size_t)rr * gpitch + n0 + c4);
-            } else {
-                const int grp = gd[u];                   // (fetched one K-tile ahead: one memory round trip here, not two)
-                ra[u] = *reinterpret_cast<const int4*>(d.argmax + (size_t)grp * gpitch + n0 + c4);
-                rg[u] = ldg4(d.dout + (size_t)grp * gpitch + n0 + c4);
-            }
-            if (XM == 0) {
-                rx[u] = ldg4(x.zin + (size_t)rr * x.zin_pitch + k0 + c4);
-            } else {
-                rx[u] = ldg4(x.feat + (size_t)pq[u] * x.feat_c + k0 + c4);
-                if (coords) {
-                    const float* p = x.src_xyz + (size_t)pq[u] * 3;
-                    float q0 = p[0], q1 = p[1], q2 = p[2];
-                    if (x.ctr_xyz) {
-                        const float* cp = x.ctr_xyz + (size_t)gq[u] * 3;
-                        q0 = __fsub_rn(q0, cp[0]); q1 = __fsub_rn(q1, cp[1]); q2 = __fsub_rn(q2, cp[2]);
-                    }
-                    rd[u][0] = q0; rd[u][1] = q1; rd[u][2] = q2;
-                }
-            }
-        }
-        if (XM == 1 || GM == 1) load_idx(rb0 + KT);
-    };
-    auto write_lds = [&](int it, int rb0) {
-        float* As = smem + (it & 1) * STAGE;
-        float* Bs = As + KT * P;
-        const float4 Pv = *reinterpret_cast<const float4*>(vP + c4), Qv = *reinterpret_cast<const float4*>(vP + VM + c4);
-        const float4 Sv = *reinterpret_cast<const float4*>(vP + 2 * VM + c4);
-        float4 s4 = f4zero(), t4 = f4zero();
-        if (XM == 0) { s4 = *reinterpret_cast<const float4*>(sv + c4); t4 = *reinterpret_cast<const float4*>(tv + c4); }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int r = rb0 + sr + 8 * u;
-            float4 g = rg[u];
-            const float4 z = rz[u];
-            if (GM == 1) {
-                g.x = ra[u].x == r ? g.x : 0.f; g.y = ra[u].y == r ? g.y : 0.f;
-                g.z = ra[u].z == r ? g.z : 0.f; g.w = ra[u].w == r ? g.w : 0.f;
-            }
-            const float w = rw[u];
-            float4 a, b;
-            a.x = Pv.x * g.x - w * fmaf(Sv.x, z.x, Qv.x); a.y = Pv.y * g.y - w * fmaf(Sv.y, z.y, Qv.y);
-            a.z = Pv.z * g.z - w * fmaf(Sv.z, z.z, Qv.z); a.w = Pv.w * g.w - w * fmaf(Sv.w, z.w, Qv.w);
-            if (XM == 0) {
-                b.x = fmaxf(fmaf(rx[u].x, s4.x, t4.x), 0.f); b.y = fmaxf(fmaf(rx[u].y, s4.y, t4.y), 0.f);
-                b.z = fmaxf(fmaf(rx[u].z, s4.z, t4.z), 0.f); b.w = fmaxf(fmaf(rx[u].w, s4.w, t4.w), 0.f);
-            } else {
-                b = rx[u];
-            }
-            if (r >= r_end) { a = f4zero(); b = f4zero(); }
-            if (coords) {
-#pragma unroll
-                for (int dd = 0; dd < 3; ++dd) {
-                    wx[0][dd] = fmaf(a.x, rd[u][dd], wx[0][dd]); wx[1][dd] = fmaf(a.y, rd[u][dd], wx[1][dd]);
-                    wx[2][dd] = fmaf(a.z, rd[u][dd], wx[2][dd]); wx[3][dd] = fmaf(a.w, rd[u][dd], wx[3][dd]);
-                }
-            }
-            *reinterpret_cast<float4*>(As + (sr + 8 * u) * P + c4) = a;
-            *reinterpret_cast<float4*>(Bs + (sr + 8 * u) * P + c4) = b;
-        }
-    };
-    if (XM == 1 || GM == 1) load_idx(r_begin);
-    load_regs(r_begin);
-    __syncthreads();                                     // vP / sv / tv visible
-    write_lds(0, r_begin);
-    if (r_begin + KT < r_end) load_regs(r_begin + KT);
-    __syncthreads();
-    int it = 0;
-    for (int rb0 = r_begin; rb0 < r_end; rb0 += KT, ++it) {
-        const float* As = smem + (it & 1) * STAGE + half * P + wm * 64 + l31;
-        const float* Bs = smem + (it & 1) * STAGE + KT * P + half * P + wn * 64 + l31;
-#pragma unroll
-        for (int s = 0; s < KT / 2; ++s) {
-            const float a0 = As[2 * s * P], a1 = As[2 * s * P + 32];
-            const float b0 = Bs[2 * s * P], b1 = Bs[2 * s * P + 32];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        if (rb0 + KT < r_end) write_lds(it + 1, rb0 + KT);
-        if (rb0 + 2 * KT < r_end) load_regs(rb0 + 2 * KT);
-        __syncthreads();
-    }
-    float* pout = partial + (size_t)blockIdx.y * n_out * Kp;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int n = n0 + wm * 64 + a * 32 + acc_row(v, half), k = k0 + wn * 64 + b * 32 + l31;
-                pout[(size_t)n * Kp + k] = acc[a][b][v];
-            }
-    if (coords) {                                        // eight staging rows per channel quad -> one sum (the tile LDS is free)
-        float* red = smem;                               // [8][128][3]
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int dd = 0; dd < 3; ++dd) red[(sr * BT + c4 + j) * 3 + dd] = wx[j][dd];
-        __syncthreads();
-        for (int i = tid; i < BT * 3; i += 256) {
-            float sum = 0.f;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) sum += red[q * BT * 3 + i];
-            pout[(size_t)(n0 + i / 3) * Kp + x.feat_c + i % 3] = sum;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// wide-tile dW in split-bf16 form (option "mfma_split", GAD_SPLIT_DW_WIDE): the same 128 x 128 block per workgroup, 64 x 64
-// per wavefront, K-tile = 32 rows.  The reduction index (rows) is the SLOW index of both operands in memory, while
-// v_mfma_f32_32x32x16_bf16 wants 8 consecutive reduction indices per lane: so a thread stages a 4-row x 4-channel patch
-// (rows 4 rq .. + 3 of the K-tile, channels 4 cq .. + 3; rq = tid & 7: a wavefront's loads cover 8 rows x 128 contiguous
-// bytes), forms dZ / the activated input in registers, splits ROW PAIRS of one channel into hi / mid / lo and stores
-// 8 bytes (four rows) per channel and plane into LDS laid out [plane][channel][32 rows] (64-byte rows, 16-byte chunks
-// XOR-swizzled by (channel >> 2) & 3: fragments are conflict-free ds_read_b128 of 8 consecutive rows).  Rows 16 .. 31 of every
-// K-tile carry NEGATED dZ and accumulate into the second accumulator set (the bf16 MFMA's truncation bias cancels in the
-// difference).  One workgroup per CU (eight accumulators per wavefront), LDS double-buffered, one barrier per K-tile.
-// ------------------------------------------------------------------------------------------------
-template <int XM, int GM>
-__global__ __launch_bounds__(256, 1) void gemm_dw_wide_split_kernel(DzSrc d, XSrc x, const int32_t* __restrict__ n_rows_dev,
-                                                                    int n_rows_static, int Kp, int n_out, int tiles_k,
-                                                                    float* __restrict__ partial, unsigned long long* __restrict__ ts) {
-    KTimer kt_(ts);
-    constexpr int BT = 128, OPL = BT * 64, STAGE = 6 * OPL, VM = 512;      // bytes: one operand plane, one stage (A planes | B planes)
-    __shared__ __attribute__((aligned(16))) unsigned char smem_b[2 * STAGE];
-    __shared__ __attribute__((aligned(16))) float vP[5 * VM];               // P | Q | S of the dZ channels, scale | shift of the input channels
-    float* sv = vP + 3 * VM;
-    float* tv = sv + VM;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int l31 = lane & 31, half = lane >> 5;
-    const int n0 = (blockIdx.x / tiles_k) * BT, k0 = (blockIdx.x % tiles_k) * BT;
-    const int n_rows = n_rows_dev ? min(*n_rows_dev, n_rows_static) : n_rows_static;
-    int chunk = gad_cdiv_dev(n_rows, (int)gridDim.y);
-    chunk = (chunk + KT - 1) / KT * KT;                  // == dw_reduce_kernel's split geometry
-    const int r_begin = blockIdx.y * chunk, r_end = min(r_begin + chunk, n_rows);
-    if (r_begin >= r_end) return;                        // the reducer skips the same splits
-    for (int i = tid; i < BT; i += 256) {
-        float Pc, Qc, Sc;
-        dz_coef(d, n0 + i, Pc, Qc, Sc, blockIdx.y == 0 && k0 == 0);
-        vP[i] = Pc; vP[VM + i] = Qc; vP[2 * VM + i] = Sc;
-        if (XM == 0) { sv[i] = x.scale[k0 + i]; tv[i] = x.shift[k0 + i]; }
-    }
-    const bool coords = XM == 1 && k0 == 0;              // this workgroup also forms dW[n][feat_c .. feat_c + 2]
-    float wx[4][3];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { wx[j][0] = 0.f; wx[j][1] = 0.f; wx[j][2] = 0.f; }
-    f32x16 acc[2][2], an[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) { acc[a][b][v] = 0.f; an[a][b][v] = 0.f; }
-    // staging patch of this thread: rows 4 rq + u (u < 4) of the K-tile, channels c4 .. c4 + 3
-    const int rq = tid & 7, c4 = (tid >> 3) * 4;
-    const float sgn = rq >= 4 ? -1.f : 1.f;              // rows 16 .. 31: negated dZ
-    const int gpitch = GM == 0 ? d.g_pitch : d.c;
-    float4 rz[4], rg[4], rx[4];
-    int4 ra[4];
-    float rw[4], rd[4][3];
-    int pq[4], gq[4], gd[4];                             // point / group of the NEXT tile's rows (gathered input, pooled gradient)
-    auto load_idx = [&](int rb0) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int r = rb0 + 4 * rq + u;
-            const int rr = r < r_end ? r : r_end - 1;
-            pq[u] = XM == 1 ? x.row_pt[rr] : 0;
-            gq[u] = (XM == 1 && x.ctr_xyz) ? x.row_grp[rr] : 0;
-            gd[u] = GM == 1 ? d.row_grp[rr] : 0;
-        }
-    };
-    auto load_regs = [&](int rb0) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int r = rb0 + 4 * rq + u;
-            const int rr = r < r_end ? r : r_end - 1;
-            rw[u] = d.row_w ? d.row_w[rr] : 1.f;
-            rz[u] = ldg4(d.z + (size_t)rr * d.z_pitch + n0 + c4);
-            if (GM == 0) {
-                rg[u] = ldg4(d.G + (size_t)rr * gpitch + n0 + c4);
-            } else {
-                const int grp = gd[u];
-                ra[u] = *reinterpret_cast<const int4*>(d.argmax + (size_t)grp * gpitch + n0 + c4);
-                rg[u] = ldg4(d.dout + (size_t)grp * gpitch + n0 + c4);
-            }
-            if (XM == 0) {
-                rx[u] = ldg4(x.zin + (size_t)rr * x.zin_pitch + k0 + c4);
-            } else {
-                rx[u] = ldg4(x.feat + (size_t)pq[u] * x.feat_c + k0 + c4);
-                if (coords) {
-                    const float* p = x.src_xyz + (size_t)pq[u] * 3;
-                    float q0 = p[0], q1 = p[1], q2 = p[2];
-                    if (x.ctr_xyz) {
-                        const float* cp = x.ctr_xyz + (size_t)gq[u] * 3;
-                        q0 = __fsub_rn(q0, cp[0]); q1 = __fsub_rn(q1, cp[1]); q2 = __fsub_rn(q2, cp[2]);
-                    }
-                    rd[u][0] = q0; rd[u][1] = q1; rd[u][2] = q2;
-                }
-            }
-        }
-        if (XM == 1 || GM == 1) load_idx(rb0 + KT);
-    };
-    // [plane][channel][rows]: this thread's 8 bytes (rows 4 rq .. + 3) of channel c4 + j
-    const int wr_off = c4 * 64 + (rq & 1) * 8, wr_q = rq >> 1;
-    auto write_lds = [&](int it, int rb0) {
-        unsigned char* As = smem_b + (it & 1) * STAGE;
-        unsigned char* Bs = As + 3 * OPL;
-        const float4 Pv = *reinterpret_cast<const float4*>(vP + c4), Qv = *reinterpret_cast<const float4*>(vP + VM + c4);
-        const float4 Sv = *reinterpret_cast<const float4*>(vP + 2 * VM + c4);
-        float4 s4 = f4zero(), t4 = f4zero();
-        if (XM == 0) { s4 = *reinterpret_cast<const float4*>(sv + c4); t4 = *reinterpret_cast<const float4*>(tv + c4); }
-        float av[4][4], bv[4][4];                        // [row u][channel j]
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int r = rb0 + 4 * rq + u;
-            float4 g = rg[u];
-            const float4 z = rz[u];
-            if (GM == 1) {
-                g.x = ra[u].x == r ? g.x : 0.f; g.y = ra[u].y == r ? g.y : 0.f;
-                g.z = ra[u].z == r ? g.z : 0.f; g.w = ra[u].w == r ? g.w : 0.f;
-            }
-            const float w = rw[u];
-            float4 a, b;
-            a.x = Pv.x * g.x - w * fmaf(Sv.x, z.x, Qv.x); a.y = Pv.y * g.y - w * fmaf(Sv.y, z.y, Qv.y);
-            a.z = Pv.z * g.z - w * fmaf(Sv.z, z.z, Qv.z); a.w = Pv.w * g.w - w * fmaf(Sv.w, z.w, Qv.w);
-            if (XM == 0) {
-                b.x = fmaxf(fmaf(rx[u].x, s4.x, t4.x), 0.f); b.y = fmaxf(fmaf(rx[u].y, s4.y, t4.y), 0.f);
-                b.z = fmaxf(fmaf(rx[u].z, s4.z, t4.z), 0.f); b.w = fmaxf(fmaf(rx[u].w, s4.w, t4.w), 0.f);
-            } else {
-                b = rx[u];
-            }
-            if (r >= r_end) { a = f4zero(); b = f4zero(); }
-            if (coords) {
-#pragma unroll
-                for (int dd = 0; dd < 3; ++dd) {
-                    wx[0][dd] = fmaf(a.x, rd[u][dd], wx[0][dd]); wx[1][dd] = fmaf(a.y, rd[u][dd], wx[1][dd]);
-                    wx[2][dd] = fmaf(a.z, rd[u][dd], wx[2][dd]); wx[3][dd] = fmaf(a.w, rd[u][dd], wx[3][dd]);
-                }
-            }
-            av[u][0] = a.x * sgn; av[u][1] = a.y * sgn; av[u][2] = a.z * sgn; av[u][3] = a.w * sgn;
-            bv[u][0] = b.x; bv[u][1] = b.y; bv[u][2] = b.z; bv[u][3] = b.w;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int off = wr_off + j * 64 + (((wr_q ^ (((c4 + j) >> 2) & 3))) << 4);
-            unsigned h0, m0, l0, h1, m1, l1;
-            gad_split2(av[0][j], av[1][j], h0, m0, l0);
-            gad_split2(av[2][j], av[3][j], h1, m1, l1);
-            *reinterpret_cast<uint2*>(As + off) = make_uint2(h0, h1);
-            *reinterpret_cast<uint2*>(As + OPL + off) = make_uint2(m0, m1);
-            *reinterpret_cast<uint2*>(As + 2 * OPL + off) = make_uint2(l0, l1);
-            gad_split2(bv[0][j], bv[1][j], h0, m0, l0);
-            gad_split2(bv[2][j], bv[3][j], h1, m1, l1);
-            *reinterpret_cast<uint2*>(Bs + off) = make_uint2(h0, h1);
-            *reinterpret_cast<uint2*>(Bs + OPL + off) = make_uint2(m0, m1);
-            *reinterpret_cast<uint2*>(Bs + 2 * OPL + off) = make_uint2(l0, l1);
-        }
-    };
-    if (XM == 1 || GM == 1) load_idx(r_begin);
-    load_regs(r_begin);
-    __syncthreads();                                     // vP / sv / tv visible
-    write_lds(0, r_begin);
-    if (r_begin + KT < r_end) load_regs(r_begin + KT);
-    __syncthreads();
-    // fragment addressing: channel rows wm * 64 + a * 32 + l31 (A) / wn * 64 + b * 32 + l31 (B); chunk 2 st + half, swizzled
-    const int fo = ((half ^ ((l31 >> 2) & 3)) << 4);
-    const int arow = (wm * 64 + l31) * 64, brow = 3 * OPL + (wn * 64 + l31) * 64;
-    int it = 0;
-    for (int rb0 = r_begin; rb0 < r_end; rb0 += KT, ++it) {
-        const unsigned char* st = smem_b + (it & 1) * STAGE;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const int off = fo ^ (s2 << 5);
-            gad_u32x4 A[2][3], B[2][3];
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
-                    A[a][pl] = *reinterpret_cast<const gad_u32x4*>(st + arow + a * (32 * 64) + pl * OPL + off);
-                    B[a][pl] = *reinterpret_cast<const gad_u32x4*>(st + brow + a * (32 * 64) + pl * OPL + off);
-                }
-            // the six products of weight >= 2^-16, smallest first: (A plane, B plane) = (lo, hi) (hi, lo) (mid, mid) (mid, hi) (hi, mid) (hi, hi)
-#define GAD_SPD(PA, PB_)                                                                                                       \
-            _Pragma("unroll") for (int a = 0; a < 2; ++a) _Pragma("unroll") for (int b = 0; b < 2; ++b) {                      \
-                if (s2) an[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gad_as_bf16x8(A[a][PA]), gad_as_bf16x8(B[b][PB_]), an[a][b], 0, 0, 0); \
-                else acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gad_as_bf16x8(A[a][PA]), gad_as_bf16x8(B[b][PB_]), acc[a][b], 0, 0, 0); \
-            }
-            GAD_SPD(2, 0) GAD_SPD(0, 2) GAD_SPD(1, 1) GAD_SPD(1, 0) GAD_SPD(0, 1) GAD_SPD(0, 0)
-#undef GAD_SPD
-        }
-        if (rb0 + KT < r_end) write_lds(it + 1, rb0 + KT);
-        if (rb0 + 2 * KT < r_end) load_regs(rb0 + 2 * KT);
-        __syncthreads();
-    }
-    float* pout = partial + (size_t)blockIdx.y * n_out * Kp;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int n = n0 + wm * 64 + a * 32 + acc_row(v, half), k = k0 + wn * 64 + b * 32 + l31;
-                pout[(size_t)n * Kp + k] = acc[a][b][v] - an[a][b][v];
-            }
-    if (coords) {                                        // 8 row quads per channel quad -> one sum (the tile LDS is free)
-        float* red = reinterpret_cast<float*>(smem_b);   // [8][128][3]
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int dd = 0; dd < 3; ++dd) red[(rq * BT + c4 + j) * 3 + dd] = wx[j][dd];
-        __syncthreads();
-        for (int i = tid; i < BT * 3; i += 256) {
-            float sum = 0.f;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) sum += red[q * BT * 3 + i];
-            pout[(size_t)(n0 + i / 3) * Kp + x.feat_c + i % 3] = sum;
-        }
-    }
-}
-
-// the wide-tile dW covers: ACT input with BatchNorm + ReLU in front, one group, 128-multiples on both sides, no bias / extra column
-static bool dw_wideable(const gad_gemm_dw_args& a, int k_used, bool vec) {
-    const gad_gemm_fwd_args& in = a.in;
-    const gad_dz_src& d = a.dz;
-    if (g_opt_deterministic || !g_opt_dw_wide || !vec || in.n_groups != 1 || in.zin_off[0] != 0 || a.dz_off[0] != 0) return false;
-    if (in.n_rows < 2048 || in.n_out[0] % 128 != 0 || in.n_out[0] > 512 || in.ones_col >= 0) return false;
-    if (in.mode == 1) {                                  // gathered first layer: features a multiple of 128, + 3 coordinates
-        if (g_opt_dw_wide == 2 || d.gmode != 0 || in.act_c != 0 || in.feat_c % 128 != 0 || in.feat_c > 512) return false;
-        if (in.Kp != ((in.feat_c + 3 + 7) & ~7) || k_used != in.feat_c + 3) return false;
-    } else {
-        if (in.Kp % 128 != 0 || in.Kp > 512 || k_used != in.Kp) return false;
-        if (in.c_in != in.Kp || !in.scale || !in.shift || !in.relu || in.extra) return false;
-    }
-    if (!d.z || d.z_pitch % 4 != 0 || !d.relu || !d.premasked || !(d.coefP && d.coefQ && d.coefS)) return false;
-    if (d.gmode == 0 ? (d.g_pitch % 4 != 0 || !d.G) : (d.c % 4 != 0)) return false;
-    return a.partial != nullptr && a.row_splits <= 0;
-}
-
-static bool dw_gather_streamable(const gad_gemm_dw_args& a, int k_used) {
-    const gad_gemm_fwd_args& in = a.in;
-    const gad_dz_src& d = a.dz;
-    if (g_opt_deterministic || !g_opt_dw_stream || in.mode != 1 || in.n_groups != 1 || in.Kp > 32 || in.n_out[0] != 64 || k_used > in.Kp) return false;
-    if (in.zin_off[0] != 0 || a.dz_off[0] != 0 || in.n_rows < 32768 || d.gmode != 0 || !d.G) return false;
-    if (!d.z || !d.scale || !d.relu || !d.premasked || !(d.coefP && d.coefQ && d.coefS)) return false;
-    if (in.feat_c + 3 + (in.action ? in.act_c : 0) > in.Kp) return false;
-    if (!a.partial || 256ll * 64 * in.Kp > a.partial_elems) return false;
-    return a.row_splits <= 0;
-}
-
-static bool dw_streamable(const gad_gemm_dw_args& a, int k_used) {
-    const gad_gemm_fwd_args& in = a.in;
-    const gad_dz_src& d = a.dz;
-    if (g_opt_deterministic || !g_opt_dw_stream || in.mode != 0 || in.n_groups != 1 || in.Kp != 64 || in.c_in != 64 || k_used != 64) return false;
-    if (in.zin_off[0] != 0 || a.dz_off[0] != 0 || (in.n_out[0] != 64 && in.n_out[0] != 128)) return false;   // w_off: arena offset, dw_reduce applies it
-    if (in.n_rows < 32768 || !in.scale || !in.shift || !in.relu || in.extra || in.ones_col >= 0) return false;
-    if (!d.z || !d.scale || !d.relu || !d.premasked || !(d.coefP && d.coefQ && d.coefS)) return false;
-    if (d.gmode != 0 && d.c != in.n_out[0]) return false;
-    if (!a.partial || (long long)DW_STREAM_SPLITS * in.n_out[0] * 64 > a.partial_elems) return false;
-    return a.row_splits <= 0;
-}
-
-// deterministic mode: the zeroed partial-dW slab of a split generic dW launch (splits past the live rows write nothing: zeros)
-static float* det_dw_slab(long long elems, void* stream) {
-    float* p = static_cast<float*>(gad_det_scratch(stream, GAD_DET_SLOTS2, (size_t)elems * sizeof(float)));
-    if (p && hipMemsetAsync(p, 0, (size_t)elems * sizeof(float), (hipStream_t)stream) != hipSuccess) {
-        gad_set_error("deterministic mode: clearing the partial dW slab failed");
-        return nullptr;
-    }
-    return p;
-}
-
-extern "C" int gad_gemm_dw(const gad_gemm_dw_args* a, void* stream) {
-    unsigned long long* ts = gad_take_timing_slot(stream);
-    GAD_REQUIRE(a && a->gacc, GAD_ERR_NULL, "gemm_dw: null pointer");
-    const gad_gemm_fwd_args& in = a->in;
-    GAD_REQUIRE(in.n_groups >= 1 && in.n_groups <= GAD_MAX_GROUPS, GAD_ERR_SHAPE, "gemm_dw: n_groups");
-    GAD_REQUIRE(in.Kp % 8 == 0, GAD_ERR_SHAPE, "gemm_dw: Kp must be a multiple of 8");
-    if (int e = check_input(in, "gemm_dw")) return e;
-    GAD_REQUIRE(a->dz.gmode == 0 ? a->dz.G != nullptr : (a->dz.argmax && a->dz.dout && a->dz.row_grp), GAD_ERR_NULL,
-                "gemm_dw: gradient source");
-    if (in.n_rows <= 0) return GAD_OK;
-    XSrc x = make_xsrc(in);
-    DzSrc d = make_dzsrc(a->dz);
-    // group g: dz channel offset dz_off[g], input channel offset zin_off[g], weights at w_off[g]
-    Groups gr = make_groups(in.n_groups, a->dz_off, in.w_off, in.zin_off, in.n_out);
-    const int nmax = max_nout(gr);
-    int k_used = in.mode == 0 ? in.c_in + (in.extra ? 1 : 0) : in.feat_c + 3 + in.act_c;
-    if (in.ones_col >= k_used) k_used = in.ones_col + 1;
-    if (k_used > in.Kp) k_used = in.Kp;
-    hipStream_t st = (hipStream_t)stream;
-    const int rows = in.n_rows;
-    const bool vec = dz_vectorizable(a->dz, a->dz_off, in.n_out, in.n_groups);
-    const bool skinny_route = !g_opt_deterministic && g_opt_dw_skinny && in.mode == 0 && a->dz.gmode == 0 && !in.n_rows_dev && rows <= 1024;
-    if (a->dz.bn_dbeta && (skinny_route || dw_gather_streamable(*a, k_used) || dw_streamable(*a, k_used))) {
-        gad_dz_src dz2 = a->dz;                          // these kernels read P / Q / S per lane: gad_bn_bwd_coef first
-        if (int e2 = coef_fallback(dz2, stream)) return e2;
-        d = make_dzsrc(dz2);
-    }
-    if (skinny_route) {
-        if (g_opt_skinny_nw == 4)
-            hipLaunchKernelGGL(gemm_dw_skinny_kernel<4>, dim3(gad_cdiv(nmax, 32), gad_cdiv(k_used, 32), gr.n), dim3(64 * 4), 0, st, d, x,
-                               gr, rows, in.Kp, k_used, a->gacc, ts);
-        else
-            hipLaunchKernelGGL(gemm_dw_skinny_kernel<SK_NW>, dim3(gad_cdiv(nmax, 32), gad_cdiv(k_used, 32), gr.n), dim3(64 * SK_NW), 0, st, d, x,
-                               gr, rows, in.Kp, k_used, a->gacc, ts);
-        GAD_CHECK_LAUNCH("gemm_dw(skinny)");
-        return GAD_OK;
-    }
-    if (dw_gather_streamable(*a, k_used)) {
-        const int splits = 256;
-        const int gps = in.grp_per_sample > 0 ? in.grp_per_sample : 1;
-        hipLaunchKernelGGL(gemm_dw_gather_stream_kernel, dim3(splits), dim3(512), 0, st, d, x, in.n_rows_dev, rows, splits, in.Kp, k_used,
-                           1.0f / (float)gps, a->partial, ts);
-        GAD_CHECK_LAUNCH("gemm_dw(gather stream)");
-        hipLaunchKernelGGL(dw_reduce_kernel, dim3(gad_cdiv((long long)nmax * in.Kp, 256), gad_cdiv(splits, DW_RED_CHUNK), gr.n), dim3(256), 0,
-                           st, a->partial, (long long)splits * nmax * in.Kp, gr, in.n_rows_dev, rows, splits, in.Kp, k_used, a->gacc, 1);
-        GAD_CHECK_LAUNCH("dw_reduce");
-        return GAD_OK;
-    }
-    if (dw_streamable(*a, k_used)) {
-        const int splits = DW_STREAM_SPLITS;
-        float* part = a->partial;
-        if (in.n_out[0] == 64) {
-            if (a->dz.gmode == 0) hipLaunchKernelGGL((gemm_dw_stream_kernel<1, 0>), dim3(splits), dim3(512), 0, st, d, x, in.n_rows_dev, rows, splits, part, ts);
-            else                  hipLaunchKernelGGL((gemm_dw_stream_kernel<1, 1>), dim3(splits), dim3(512), 0, st, d, x, in.n_rows_dev, rows, splits, part, ts);
-        } else {
-            if (a->dz.gmode == 0) hipLaunchKernelGGL((gemm_dw_stream_kernel<2, 0>), dim3(splits), dim3(512), 0, st, d, x, in.n_rows_dev, rows, splits, part, ts);
-            else                  hipLaunchKernelGGL((gemm_dw_stream_kernel<2, 1>), dim3(splits), dim3(512), 0, st, d, x, in.n_rows_dev, rows, splits, part, ts);
-        }
-        GAD_CHECK_LAUNCH("gemm_dw(stream)");
-        hipLaunchKernelGGL(dw_reduce_kernel, dim3(gad_cdiv((long long)nmax * in.Kp, 256), gad_cdiv(splits, DW_RED_CHUNK), gr.n), dim3(256), 0,
-                           st, part, (long long)splits * nmax * in.Kp, gr, in.n_rows_dev, rows, splits, in.Kp, k_used, a->gacc, 1);
-        GAD_CHECK_LAUNCH("dw_reduce");
-        return GAD_OK;
-    }
-    if (dw_wideable(*a, k_used, vec)) {
-        const int tn_ = in.n_out[0] / 128, tk_ = (in.mode == 1 ? in.feat_c : in.Kp) / 128;
-        int splits = gad_cdiv(g_opt_dw_wide_wgs, tn_ * tk_);             // ~one workgroup per CU
-        const int by_rows = gad_cdiv(rows, 4 * KT);
-        if (splits > by_rows) splits = by_rows;
-        if (splits < 1) splits = 1;
-        if ((long long)splits * in.n_out[0] * in.Kp <= a->partial_elems && split_on(GAD_SPLIT_DW_WIDE)) {
-            // split-bf16 products: both operands are formed and split by the kernel itself (no weight mirror involved)
-#define LAUNCH_DWS(XM, GM)                                                                                                     \
-            hipLaunchKernelGGL((gemm_dw_wide_split_kernel<XM, GM>), dim3(tn_ * tk_, splits), dim3(256), 0, st, d, x, in.n_rows_dev, rows, \
-                               in.Kp, in.n_out[0], tk_, a->partial, ts)
-            if (in.mode == 1) LAUNCH_DWS(1, 0); else if (a->dz.gmode == 0) LAUNCH_DWS(0, 0); else LAUNCH_DWS(0, 1);
-#undef LAUNCH_DWS
-            GAD_CHECK_LAUNCH("gemm_dw(wide split)");
-            hipLaunchKernelGGL(dw_reduce_kernel, dim3(gad_cdiv((long long)nmax * in.Kp, 256), gad_cdiv(splits, DW_RED_CHUNK), gr.n), dim3(256),
-                               0, st, a->partial, (long long)splits * nmax * in.Kp, gr, in.n_rows_dev, rows, splits, in.Kp, k_used, a->gacc);
-            GAD_CHECK_LAUNCH("dw_reduce");
-            return GAD_OK;
-        }
-        if ((long long)splits * in.n_out[0] * in.Kp <= a->partial_elems) {
-            if (in.mode == 1)
-                hipLaunchKernelGGL((gemm_dw_wide_kernel<1, 0>), dim3(tn_ * tk_, splits), dim3(256), 0, st, d, x, in.n_rows_dev, rows, in.Kp,
-                                   in.n_out[0], tk_, a->partial, ts);
-            else if (a->dz.gmode == 0)
-                hipLaunchKernelGGL((gemm_dw_wide_kernel<0, 0>), dim3(tn_ * tk_, splits), dim3(256), 0, st, d, x, in.n_rows_dev, rows, in.Kp,
-                                   in.n_out[0], tk_, a->partial, ts);
-            else
-                hipLaunchKernelGGL((gemm_dw_wide_kernel<0, 1>), dim3(tn_ * tk_, splits), dim3(256), 0, st, d, x, in.n_rows_dev, rows, in.Kp,
-                                   in.n_out[0], tk_, a->partial, ts);
-            GAD_CHECK_LAUNCH("gemm_dw(wide)");
-            hipLaunchKernelGGL(dw_reduce_kernel, dim3(gad_cdiv((long long)nmax * in.Kp, 256), gad_cdiv(splits, DW_RED_CHUNK), gr.n), dim3(256),
-                               0, st, a->partial, (long long)splits * nmax * in.Kp, gr, in.n_rows_dev, rows, splits, in.Kp, k_used, a->gacc);
-            GAD_CHECK_LAUNCH("dw_reduce");
-            return GAD_OK;
-        }
-    }
-    long long group_stride = 0;
-#define LAUNCH_DW4(WM, WN, TM, TN, XM, V, VM)                                                              \
-    hipLaunchKernelGGL((gemm_dw_kernel<WM, WN, TM, TN, XM, V, VM>), dim3(tn_ * tk_, splits, gr.n), dim3(256), 0, st, d, \
-                       x, gr, in.n_rows_dev, rows, in.Kp, k_used, tk_, a->gacc, part, group_stride, ts)
-#define LAUNCH_DW3(WM, WN, TM, TN, XM, V)                                                                  \
-    do { if (narrow) LAUNCH_DW4(WM, WN, TM, TN, XM, V, 512); else LAUNCH_DW4(WM, WN, TM, TN, XM, V, VMAX); } while (0)
-#define LAUNCH_DW(WM, WN, TM, TN)                                                                          \
-    do {                                                                                                   \
-        constexpr int BM = WM * TM * 32, BN = WN * TN * 32;                                                \
-        const int tn_ = gad_cdiv(nmax, BM), tk_ = gad_cdiv(k_used, BN);                                    \
-        splits = a->row_splits;                                                                            \
-        if (splits <= 0) {                                                                                 \
-            splits = gad_cdiv(512, tn_ * tk_ * gr.n);                     /* 256 / 1024 / 2048 measured slower */                                                    \
-            const int by_rows = gad_cdiv(rows, 8 * KT);                                                    \
-            if (splits > by_rows) splits = by_rows;                                                        \
-            if (splits < 1) splits = 1;                                                                    \
-        }                                                                                                  \
-        group_stride = (long long)splits * nmax * in.Kp;                                                   \
-        if (part && (splits == 1 || group_stride * gr.n > a->partial_elems)) part = nullptr; \
-        if (g_opt_deterministic) {               /* every split's partial into the mode's zeroed slab, summed in order */ \
-            part = splits > 1 ? det_dw_slab(group_stride * gr.n, stream) : nullptr;                       \
-            if (splits > 1 && !part) return GAD_ERR_LAUNCH;                                                \
-        }                                                                                                  \
-        if (in.mode == 0) { if (vec) LAUNCH_DW3(WM, WN, TM, TN, 0, true); else LAUNCH_DW3(WM, WN, TM, TN, 0, false); } \
-        else              { if (vec) LAUNCH_DW3(WM, WN, TM, TN, 1, true); else LAUNCH_DW3(WM, WN, TM, TN, 1, false); } \
-    } while (0)
-    int splits = 1;
-    float* part = a->partial;
-    const bool narrow = nmax <= 512 && (in.mode != 0 || in.c_in <= 512);   // per-channel vectors fit a 512-float stride
-    if (nmax <= 32) {
-        LAUNCH_DW(1, 4, 1, 1);      // 32 x 128
-    } else if (k_used <= 32) {
-        LAUNCH_DW(4, 1, 1, 1);      // 128 x 32
-    } else {
-        LAUNCH_DW(2, 2, 1, 1);      // 64 x 64
-    }
-#undef LAUNCH_DW
-#undef LAUNCH_DW3
-#undef LAUNCH_DW4
-    GAD_CHECK_LAUNCH("gemm_dw");
-    if (part && g_opt_deterministic) {
-        for (int g = 0; g < gr.n; ++g)
-            if (int e = gad_ordered_reduce(part + (size_t)g * group_stride, (long long)gr.nout[g] * in.Kp, splits,
-                                           (long long)gr.nout[g] * in.Kp, a->gacc + gr.woff[g], stream)) return e;
-    } else if (part) {
-        hipLaunchKernelGGL(dw_reduce_kernel, dim3(gad_cdiv((long long)nmax * in.Kp, 256), gad_cdiv(splits, DW_RED_CHUNK), gr.n),
-                           dim3(256), 0, st, part,
-                           group_stride, gr, in.n_rows_dev, rows, splits, in.Kp, k_used, a->gacc);
-        GAD_CHECK_LAUNCH("dw_reduce");
-    }
     return GAD_OK;
 }
 
@@ -5223,7 +3367,7 @@ __global__ __launch_bounds__(256, NIT >= 8 ? 1 : 2) void gemm_bwd_wide_kernel(Dz
 // workgroups per k block of a fused wide launch = partial dW blocks it writes (static: the reduce launch recomputes it)
 static int bwd_wide_splits(const gad_gemm_dx_args& ax) {
     const long long per = (long long)ax.n_out[0] * ax.Kp;
-    long long g = (long long)g_opt_bwd_wide_slab * 1000000ll / per;
+    long long g = (long long)g_opt.bwd_wide_slab * 1000000ll / per;
     const int tiles = gad_cdiv(ax.n_rows, 64);
     const int kb = ax.k_valid / 64;
     if (g * kb > 1024) g = 1024 / kb;                    // (no more workgroups than fit the chip at once)
@@ -5240,11 +3384,11 @@ static int bwd_wide_splits(const gad_gemm_dx_args& ax) {
 // sides (premasked gradients), N in {128, 256, 512}, K a multiple of 64; the gathered first layers with their scatter epilogue
 static bool bwd_wideable(const gad_gemm_dx_args& ax, const gad_gemm_dw_args& aw, bool vec) {
     const gad_gemm_fwd_args& in = aw.in;
-    if (g_opt_deterministic || !g_opt_bwd_wide || !vec || ax.n_groups != 1 || in.n_groups != 1) return false;
+    if (g_opt.deterministic || !g_opt.bwd_wide || !vec || ax.n_groups != 1 || in.n_groups != 1) return false;
     if (ax.dz_off[0] != 0 || ax.w_off[0] != 0 || ax.gout_off[0] != 0 || in.zin_off[0] != 0 || aw.dz_off[0] != 0) return false;
     const int N = ax.n_out[0];
     if (N != 128 && N != 256 && N != 512) return false;
-    if (ax.n_rows < 2048 || (g_opt_bwd_wide == 2 && ax.n_rows < 16384) || ax.n_rows != in.n_rows || ax.n_rows_dev != in.n_rows_dev) return false;
+    if (ax.n_rows < 2048 || (g_opt.bwd_wide == 2 && ax.n_rows < 16384) || ax.n_rows != in.n_rows || ax.n_rows_dev != in.n_rows_dev) return false;
     if (in.n_out[0] != N || in.Kp != ax.Kp || in.ones_col >= 0 || !aw.partial || !aw.gacc || !ax.W) return false;
     if (ax.k_valid % 64 != 0 || ax.k_valid < 64 || (long long)bwd_wide_splits(ax) * N * ax.Kp > aw.partial_elems) return false;   // (workspace of another route)
     const gad_dz_src& d = ax.dz;
@@ -5266,7 +3410,7 @@ static bool bwd_wideable(const gad_gemm_dx_args& ax, const gad_gemm_dw_args& aw,
 
 static bool bwd_streamable(const gad_gemm_dx_args* ax, const gad_gemm_dw_args* aw) {
     const gad_gemm_fwd_args& in = aw->in;
-    if (g_opt_deterministic || !g_opt_bwd_fused) return false;
+    if (g_opt.deterministic || !g_opt.bwd_fused) return false;
     const bool vec = dz_vectorizable(ax->dz, ax->dz_off, ax->n_out, ax->n_groups);
     int k_used = in.mode == 0 ? in.c_in + (in.extra ? 1 : 0) : in.feat_c + 3 + in.act_c;
     bool fused = dx_streamable(*ax, vec) && dw_streamable(*aw, k_used);
@@ -5290,19 +3434,13 @@ extern "C" int gad_gemm_dw_reduce(const gad_gemm_dx_args* ax, const gad_gemm_dw_
         const int splits = bwd_wide_splits(*ax);
         const int k_used = in.mode == 1 ? in.feat_c + 3 : in.Kp;
         Groups gr = make_groups(1, aw->dz_off, in.w_off, in.zin_off, in.n_out);
-        hipLaunchKernelGGL(dw_reduce_kernel, dim3(gad_cdiv((long long)in.n_out[0] * in.Kp, 256), gad_cdiv(splits, DW_RED_CHUNK), 1), dim3(256), 0,
-                           st, aw->partial, (long long)splits * in.n_out[0] * in.Kp, gr, in.n_rows_dev, ax->n_rows, splits, in.Kp, k_used,
-                           aw->gacc, 1);
-        GAD_CHECK_LAUNCH("dw_reduce");
-        return GAD_OK;
+        return dw_reduce_launch(aw->partial, gr, in.n_out[0], in.n_rows_dev, ax->n_rows, splits, in.Kp, k_used, aw->gacc, 1, st);
     }
     if (streamable) {
-        const int wgs = g_opt_bwd_stream_wgs;
+        const int wgs = g_opt.bwd_stream_wgs;
         const int splits = ax->n_out[0] == 64 ? 2 * wgs : wgs;
         Groups gr = make_groups(1, aw->dz_off, in.w_off, in.zin_off, in.n_out);
-        hipLaunchKernelGGL(dw_reduce_kernel, dim3(gad_cdiv((long long)in.n_out[0] * 64, 256), gad_cdiv(splits, DW_RED_CHUNK), 1), dim3(256), 0, st,
-                           aw->partial, (long long)splits * in.n_out[0] * 64, gr, in.n_rows_dev, ax->n_rows, splits, 64, 64, aw->gacc, 1);
-        GAD_CHECK_LAUNCH("dw_reduce");
+        return dw_reduce_launch(aw->partial, gr, in.n_out[0], in.n_rows_dev, ax->n_rows, splits, 64, 64, aw->gacc, 1, st);
     }
     return GAD_OK;
 }
@@ -5322,12 +3460,9 @@ extern "C" int gad_gemm_bwd(const gad_gemm_dx_args* ax, const gad_gemm_dw_args* 
                     (long long)splits * N * in.Kp);
         DzSrc d = make_dzsrc(ax->dz);
         XSrc x = make_xsrc(in);
-        DxEpi e;
-        e.mode = ax->epilogue; e.gout = ax->gout; e.gout_pitch = ax->gout_pitch; e.k_valid = ax->k_valid;
-        e.zprev = ax->zprev; e.zprev_pitch = ax->zprev_pitch; e.ps = ax->prev_scale; e.pt = ax->prev_shift;
-        e.pm = ax->prev_mean; e.pi = ax->prev_istd; e.dbeta = ax->prev_dbeta; e.dgamma = ax->prev_dgamma;
-        e.stat_stride = ax->stat_stride; e.store_masked = 1;
-        e.dfeat = ax->dfeat; e.feat_c = ax->feat_c; e.row_pt = ax->row_pt; e.row_grp = ax->row_grp; e.daction = nullptr; e.act_c = 0; e.gps = 1;
+        DxEpi e = make_dxepi(*ax);                                    // stores masked; the feature scatter only (bwd_wideable: no daction)
+        e.store_masked = 1;
+        e.daction = nullptr; e.act_c = 0; e.gps = 1;
         hipStream_t st = (hipStream_t)stream;
         const dim3 grid(splits, ax->k_valid / 64);
 #define LAUNCH_BWW(NIT, GM, L1) hipLaunchKernelGGL((gemm_bwd_wide_kernel<NIT, GM, L1>), grid, dim3(256), 0, st, d, x, ax->n_rows_dev, ax->n_rows, ax->W, ax->Kp, e, aw->partial, ts)
@@ -5350,14 +3485,11 @@ extern "C" int gad_gemm_bwd(const gad_gemm_dx_args* ax, const gad_gemm_dw_args* 
     GAD_REQUIRE(aw->gacc && ax->W, GAD_ERR_NULL, "gemm_bwd: null pointer");
     if (ax->n_rows <= 0) return GAD_OK;
     DzSrc d = make_dzsrc(ax->dz);
-    DxEpi e;
-    e.mode = 0; e.gout = ax->gout; e.gout_pitch = ax->gout_pitch; e.k_valid = ax->k_valid;
-    e.zprev = ax->zprev; e.zprev_pitch = ax->zprev_pitch; e.ps = ax->prev_scale; e.pt = ax->prev_shift;
-    e.pm = ax->prev_mean; e.pi = ax->prev_istd; e.dbeta = ax->prev_dbeta; e.dgamma = ax->prev_dgamma;
-    e.stat_stride = ax->stat_stride; e.store_masked = 1;
+    DxEpi e = make_dxepi(*ax);                                        // stores masked, scatters nothing
+    e.mode = 0; e.store_masked = 1;
     e.dfeat = nullptr; e.feat_c = 0; e.row_pt = nullptr; e.row_grp = nullptr; e.daction = nullptr; e.act_c = 0; e.gps = 1;
     hipStream_t st = (hipStream_t)stream;
-    const int rows = ax->n_rows, wgs = g_opt_bwd_stream_wgs;
+    const int rows = ax->n_rows, wgs = g_opt.bwd_stream_wgs;
     const int splits = ax->n_out[0] == 64 ? 2 * wgs : wgs;            // partial dW blocks the kernel writes (see its header)
     GAD_REQUIRE((long long)splits * in.n_out[0] * 64 <= aw->partial_elems, GAD_ERR_SHAPE, "gemm_bwd: partial workspace too small");
     // (a pooled source with 64 outputs -- no layer of the step: SA1 pools its 128-output layer -- keeps the FP32-MFMA kernel: the

@@ -74,7 +74,7 @@ def segment_pool(z, off, scale=None, shift=None):
 
 # ----------------------------------------------------------------------------- max-pool folded into the GEMM epilogue
 def pool_ord(v):
-    """order-preserving bits of a float32 (csrc/gemm.hip pool_ord): unsigned compare == float compare"""
+    """order-preserving bits of a float32 (csrc/gemm_common.hpp pool_ord): unsigned compare == float compare"""
     u = np.ascontiguousarray(np.asarray(v, np.float32)).view(np.uint32)
     return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
 
@@ -89,7 +89,7 @@ def pool_sign(gamma):
 
 
 def pool_keys(z, off, gamma):
-    """the packed keys the GEMM epilogue leaves (csrc/gemm.hip pool_ord / pool_put): per (group, channel) the maximum over the
+    """the packed keys the GEMM epilogue leaves (csrc/gemm_common.hpp pool_ord / pool_put): per (group, channel) the maximum over the
     group's rows of  pool_ord(sgn(gamma) * z) << 32 | (0xffffffff - row),  sgn = -1 for gamma < 0, else +1 -- the largest
     sgn * z, among equal values the smallest row.  -> uint64 (G, C)"""
     z, off = np.asarray(z, np.float32), np.asarray(off, np.int64)

@@ -94,6 +94,38 @@ def test_argument_errors_are_status_codes_not_crashes():
     assert hip.get_option_default("mfma_split") in (0, 1)
 
 
+def test_every_gemm_option_is_accepted_and_out_of_range_values_fall_back():
+    """gad_set_option's table (csrc/gemm.hip): each of the 20 GEMM options takes its default; a value outside an option's range is
+    replaced by its fallback, not refused (workgroup counts and the slab bound: non-positive -> default, bwd_stream_wgs above 256 ->
+    256, skinny_nw anything but 4 -> 8, deterministic normalised to 0 / 1) -- nothing is launched, so what is observable here is the
+    status; an unknown name is still refused."""
+    from ga_ddpg_amd import hip
+    L = hip.lib()
+    defaults = {"mfma_split": hip.get_option_default("mfma_split"), "deterministic": hip.get_option_default("deterministic"),
+                "fwd_wide": 1, "dx_wide": 1, "dw_wide": 1, "bwd_fused": 1, "fwd_bn_prologue": 1, "bwd_wide": 0, "bwd_wide_slab": 4,
+                "dw_wide_wgs": 256, "skinny_nw": 8, "fwd_skinny": 1, "dx_skinny": 1, "dx_stream": 1, "dw_skinny": 1, "dw_stream": 1,
+                "fwd_stream": 1, "bwd_stream_wgs": 256, "fwd_stream_wgs": 256, "fwd_stream_l1_wgs": 256}
+    assert len(defaults) == 20
+    try:
+        for name, v in defaults.items():
+            assert L.gad_set_option(name.encode(), v) == 0, name
+        for name in ("bwd_stream_wgs", "fwd_stream_wgs", "fwd_stream_l1_wgs", "dw_wide_wgs", "bwd_wide_slab"):
+            for v in (0, -5, 2 ** 31 - 1):
+                assert L.gad_set_option(name.encode(), v) == 0, (name, v)
+        for v in (257, 1 << 20):
+            assert L.gad_set_option(b"bwd_stream_wgs", v) == 0
+        for v in (0, 3, 5, 16, -4):
+            assert L.gad_set_option(b"skinny_nw", v) == 0
+        for v in (1, 7, -1, 0, 0):                                 # (1 -> 0 releases the mode's scratch: none was allocated)
+            assert L.gad_set_option(b"deterministic", v) == 0
+        assert L.gad_set_option(b"fwd_widee", 1) < 0 and b"unknown option 'fwd_widee'" in L.gad_last_error()
+        assert L.gad_set_option(b"", 1) < 0 and b"unknown option" in L.gad_last_error()
+        assert L.gad_set_option(None, 1) < 0 and b"null name" in L.gad_last_error()
+    finally:
+        for name, v in defaults.items():
+            hip.set_option(name, v)
+
+
 def test_plan_items_are_checked_against_the_entry_points_signature():
     """step replay (include/gaddpg.h section H): a launch item's argument words are checked against the real signature of
     the entry point when the item is added -- count and kind -- so a replay cannot mis-call the ABI.  No GPU needed: nothing

@@ -3,15 +3,18 @@
 // sanitizer build: the workspace sizes, every refusing argument path and the calls with nothing to do, none of which launches
 // anything -- so it runs on a machine without a GPU.  (The expectations on the two grid entry points are those of
 // tests/test_ball_query_grid_host.py and tests/test_three_nn_grid_host.py, those on the observation entry points of
-// tests/test_point_state_host.py.)  Build it together
+// tests/test_point_state_host.py.)  It also runs gad_set_option's table over every GEMM option and the first refusals of the GEMM
+// entry points (the expectations of tests/test_abi.py).  Build it together
 // with the library's sources, host code instrumented, and run it as it is:
 //
 //   cd ga-ddpg_amd/csrc && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -I../../include -munsafe-fp-atomics \
 //       -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
-//       ../../tools/fps_tiled_host_check.cpp geometry.hip point_grid.hip observe.hip gemm.hip layers.hip losses.hip optim.hip plan.hip \
+//       ../../tools/fps_tiled_host_check.cpp geometry.hip point_grid.hip observe.hip gemm.hip gemm_dw.hip layers.hip losses.hip optim.hip \
+//       plan.hip \
 //       -o fps_tiled_host_check
 //
 // Exit status 0 and "ok" on success; a failed expectation prints its line and exits 1.
+#include <initializer_list>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -174,6 +177,45 @@ int main() {
     EXPECT(gad_point_state_pack(p, 0, nullptr, nullptr, p, -6, 1.f, 1, 4, p, nullptr) == GAD_ERR_SHAPE && says("n_lead=-6"));
     EXPECT(gad_point_state_pack(p, 0, nullptr, nullptr, p, 2147483647, 1.f, 1, 2147483647, p, nullptr) == GAD_ERR_SHAPE && says("beyond 2^31"));
     EXPECT(gad_point_state_pack(nullptr, 0, nullptr, nullptr, nullptr, 0, 1.f, 4, 0, nullptr, nullptr) == GAD_OK);   // no column: no launch
+
+    // gad_set_option's table (gemm.hip): every GEMM option takes its default; out-of-range values fall back instead of being refused
+    // (the expectations of tests/test_abi.py); defaults again at the end
+    static const struct { const char* name; int def; } opts[20] = {
+        {"mfma_split", 0}, {"deterministic", 0}, {"fwd_wide", 1}, {"dx_wide", 1}, {"dw_wide", 1}, {"bwd_fused", 1}, {"fwd_bn_prologue", 1},
+        {"bwd_wide", 0}, {"bwd_wide_slab", 4}, {"dw_wide_wgs", 256}, {"skinny_nw", 8}, {"fwd_skinny", 1}, {"dx_skinny", 1}, {"dx_stream", 1},
+        {"dw_skinny", 1}, {"dw_stream", 1}, {"fwd_stream", 1}, {"bwd_stream_wgs", 256}, {"fwd_stream_wgs", 256}, {"fwd_stream_l1_wgs", 256}};
+    for (const auto& o : opts) EXPECT(gad_set_option(o.name, o.def) == GAD_OK);
+    for (const char* name : {"bwd_stream_wgs", "fwd_stream_wgs", "fwd_stream_l1_wgs", "dw_wide_wgs", "bwd_wide_slab"})
+        for (int v : {0, -5, 2147483647, 257}) EXPECT(gad_set_option(name, v) == GAD_OK);
+    for (int v : {0, 3, 5, 16, -4, 4}) EXPECT(gad_set_option("skinny_nw", v) == GAD_OK);
+    for (int v : {1, 7, -1, 0, 0}) EXPECT(gad_set_option("deterministic", v) == GAD_OK);      // 1 -> 0 releases the (empty) scratch
+    for (int v : {-2147483647 - 1, 2147483647}) EXPECT(gad_set_option("mfma_split", v) == GAD_OK);
+    EXPECT(gad_set_option("fwd_widee", 1) == GAD_ERR_SHAPE && says("unknown option 'fwd_widee'"));
+    EXPECT(gad_set_option("", 1) == GAD_ERR_SHAPE && says("unknown option"));
+    EXPECT(gad_set_option(nullptr, 1) == GAD_ERR_NULL && says("null name"));
+    for (const auto& o : opts) EXPECT(gad_set_option(o.name, o.def) == GAD_OK);
+
+    // the first checks of the GEMM entry points: refused before anything is launched
+    gad_gemm_fwd_args fa;
+    memset(&fa, 0, sizeof fa);
+    EXPECT(gad_gemm_fwd(nullptr, nullptr) == GAD_ERR_NULL && says("null pointer"));
+    fa.W = p; fa.zout = p; fa.n_groups = 7; fa.Kp = 8;
+    EXPECT(gad_gemm_fwd(&fa, nullptr) == GAD_ERR_SHAPE && says("n_groups"));
+    fa.n_groups = 1; fa.Kp = 12;
+    EXPECT(gad_gemm_fwd(&fa, nullptr) == GAD_ERR_SHAPE && says("Kp=12"));
+    gad_gemm_dx_args xa;
+    memset(&xa, 0, sizeof xa);
+    EXPECT(gad_gemm_dx(&xa, nullptr) == GAD_ERR_NULL && says("gemm_dx: null pointer"));
+    EXPECT(gad_gemm_dx(nullptr, nullptr) == GAD_ERR_NULL);
+    gad_gemm_dw_args wa;
+    memset(&wa, 0, sizeof wa);
+    EXPECT(gad_gemm_dw(nullptr, nullptr) == GAD_ERR_NULL && says("gemm_dw: null pointer"));
+    EXPECT(gad_gemm_dw(&wa, nullptr) == GAD_ERR_NULL && says("gemm_dw: null pointer"));           // no gacc
+    EXPECT(gad_gemm_bwd(nullptr, &wa, nullptr) == GAD_ERR_NULL && says("gemm_bwd: null pointer"));
+    EXPECT(gad_gemm_bwd(&xa, nullptr, nullptr) == GAD_ERR_NULL && says("gemm_bwd: null pointer"));
+    EXPECT(gad_gemm_dw_reduce(nullptr, &wa, nullptr) == GAD_ERR_NULL && says("gemm_dw_reduce: null pointer"));
+    EXPECT(gad_gemm_dw_reduce(&xa, nullptr, nullptr) == GAD_ERR_NULL && says("gemm_dw_reduce: null pointer"));
+    EXPECT(gad_gemm_dw_reduce(&xa, &wa, nullptr) == GAD_OK);                                        // no rows: nothing to reduce
     if (g_failed) return 1;
     printf("ok\n");
     return 0;

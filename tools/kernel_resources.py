@@ -1,5 +1,5 @@
 """VGPR / AGPR / scratch / occupancy / LDS of the kernels in a hipcc -Rpass-analysis=kernel-resource-usage log.
-usage: hipcc ... -Rpass-analysis=kernel-resource-usage -c gemm.hip -o /tmp/x.o 2> /tmp/ru.txt; python tools/kernel_resources.py /tmp/ru.txt [substring]"""
+usage: hipcc ... -Rpass-analysis=kernel-resource-usage -c gemm_dw.hip -o /tmp/x.o 2> /tmp/ru.txt  (any unit of csrc/; logs may be concatenated); python tools/kernel_resources.py /tmp/ru.txt [substring]"""
 import re
 import subprocess
 import sys
