@@ -113,6 +113,7 @@ const std::vector<reg_entry>& registry() {
         GAD_PLAN_ENTRY(gad_gemm_dw)
         GAD_PLAN_ENTRY(gad_gemm_bwd)
         GAD_PLAN_ENTRY(gad_gemm_dw_reduce)
+        GAD_PLAN_ENTRY(gad_sa_coord_grad)
         GAD_PLAN_ENTRY(gad_critic_loss)
         GAD_PLAN_ENTRY(gad_policy_outputs)
         GAD_PLAN_ENTRY(gad_actor_loss)

@@ -54,11 +54,20 @@ class PointnetSAModuleMSG(nn.Module):
     pass repeats the furthest point sampling (npoint + 1 launches per scale for a cloud gad_fps_tiled takes); sharing it between
     the scales is left undone.  The only refusal left on the fused path is a shape whose rows overflow the layer kernels' 32-bit
     indexing (RuntimeError with the sizes).  engine.Geometry -- the update step and feature_forward, not these modules -- keeps
-    the LDS sampler and its refusals (include/gaddpg.h: N <= 16384, npoint <= N, (3N + npoint + 64) * 4 bytes within 160 KiB)."""
+    the LDS sampler and its refusals (include/gaddpg.h: N <= 16384, npoint <= N, (3N + npoint + 64) * 4 bytes within 160 KiB).
 
-    def __init__(self, npoint, radii, nsamples, mlps, bn=True, use_xyz=True):
+    coordinate_grad (keyword-only, default False; a plain attribute that may be set after construction, not part of state_dict):
+    upstream's module is differentiable in xyz -- grouped_xyz - new_xyz enters the first convolution, new_xyz is a gather of xyz --
+    and so is _generic_forward.  The fused path treats xyz as geometry unless this switch is on: off, xyz.grad stays None and
+    new_xyz does not require a gradient, whatever xyz.requires_grad says (GA-DDPG slices xyz out of a tensor that requires one for
+    other reasons).  On, and only where xyz.requires_grad with gradients enabled, new_xyz is differentiable and xyz.grad receives
+    what upstream's would (gad_sa_coord_grad; ga_ddpg_amd.sa_function); such a call is refused (RuntimeError at the forward) in
+    eval mode and while hip.deterministic() is in force.  The sampling and the ball query stay non-differentiable, as upstream."""
+
+    def __init__(self, npoint, radii, nsamples, mlps, bn=True, use_xyz=True, *, coordinate_grad=False):
         super().__init__()
         self.bn, self.use_xyz = bool(bn), bool(use_xyz)
+        self.coordinate_grad = bool(coordinate_grad)
         self.npoint = npoint
         self.radii, self.nsamples = list(radii), list(nsamples)
         self.radius, self.nsample = radii[0], nsamples[0]
@@ -101,14 +110,16 @@ class PointnetSAModuleMSG(nn.Module):
         new_xyz, outs = None, []
         for sc in self._scales:
             sc.train(self.training)
+            sc.coordinate_grad = self.coordinate_grad
             new_xyz, f = sa_module_forward(sc, xyz, features)
             outs.append(f)
         return new_xyz, torch.cat(outs, dim=1)
 
 
 class PointnetSAModule(PointnetSAModuleMSG):
-    def __init__(self, mlp, npoint=None, radius=None, nsample=None, bn=True, use_xyz=True):
-        super().__init__(npoint=npoint, radii=[radius], nsamples=[nsample], mlps=[mlp], bn=bn, use_xyz=use_xyz)
+    def __init__(self, mlp, npoint=None, radius=None, nsample=None, bn=True, use_xyz=True, *, coordinate_grad=False):
+        super().__init__(npoint=npoint, radii=[radius], nsamples=[nsample], mlps=[mlp], bn=bn, use_xyz=use_xyz,
+                         coordinate_grad=coordinate_grad)
 
 
 class PointnetFPModule(nn.Module):

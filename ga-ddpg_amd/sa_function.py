@@ -9,9 +9,15 @@ Differentiable: the forward is wrapped in a torch.autograd.Function whose backwa
 dX / dW kernels as the fused update step (BatchNorm-backward with weighted statistics, max-pool routing
 through the saved arg-max, scatter-add into the point features), so a network written against upstream's
 `pointnet2_ops` -- the reference's own core/networks.py:66-81,217-220 -- trains through this package
-with ordinary torch optimizers.  Gradients: wrt `features` and every parameter of the module; `xyz`
-is geometry (FPS / ball-query indices are not differentiable upstream either; the recentred xyz channels'
-gradient wrt the coordinates is not produced -- GA-DDPG never asks for it: xyz is detached).
+with ordinary torch optimizers.  Gradients: wrt `features` and every parameter of the module.  `xyz` is
+geometry by default (FPS / ball-query indices are not differentiable upstream either; GA-DDPG never asks for
+the coordinates' gradient: xyz is detached and new_xyz is not differentiable).  The module attribute
+`coordinate_grad` (pointnet2_modules: keyword-only, default False) switches upstream's coordinate path on: with
+it set and xyz.requires_grad, the recentred xyz channels of the first convolution are differentiated by
+gad_sa_coord_grad (one call behind the first layer's dX, same dZ descriptor) -- + to every row's point, - to its
+group's centroid point, plus whatever arrives through new_xyz, which is then differentiable as well (the GroupAll
+form has no centroid terms).  Refused at forward time with the switch live: eval mode (as for every backward
+here) and the library's deterministic mode (the scatter is float atomics; there is no ordered form).
 Upstream semantics mirrored: _PointnetSAModuleBase.forward: returns
 (new_xyz (B,npoint,3) | None, new_features (B, mlp[-1], npoint | 1)).
 """
@@ -119,6 +125,7 @@ class _StageRun(object):
             self.dfeat = torch.zeros(B * N, net.c_pad, **f32)
             self.grad = torch.zeros(net.flat.n, **f32)        # this call's parameter gradients (master layout)
             self.bwd = self._plan_backward(net)
+        self.bwd_xyz = None                                   # the backward plan with the coordinate gradient (coord_backward)
 
     def _workspace(self, name, *shape):
         ws = self.workspaces.get(name)
@@ -195,13 +202,30 @@ class _StageRun(object):
                       r["off"], r["G"], self.F, self.argmax)
         return plan
 
-    def _plan_backward(self, net):
+    def coord_backward(self, net):
+        """the backward plan of a call whose xyz asks for its gradient (module switch `coordinate_grad`): built on first use, with the
+        buffers only that plan needs -- dxyz (B*N, 3), the per-group sums dctr (G, 3), the incoming gradient of new_xyz and the
+        centroids' global point numbers b * N + fps (refreshed by the backward: the forward plan leaves fps)"""
+        if self.bwd_xyz is None:
+            dev, G = self.xyz.device, self.rows["G"]
+            f32 = dict(dtype=torch.float32, device=dev)
+            self.dxyz = torch.zeros(self.B * self.N, 3, **f32)
+            if not self.group_all:
+                self.dctr = torch.zeros(G, 3, **f32)
+                self.g_new = torch.zeros(G, 3, **f32)
+                self.ctr = torch.zeros(self.B, self.M, dtype=torch.int32, device=dev)
+                self.pt0 = (torch.arange(self.B, dtype=torch.int32, device=dev) * self.N).view(self.B, 1)
+            self.bwd_xyz = self._plan_backward(net, coord=True)
+        return self.bwd_xyz
+
+    def _plan_backward(self, net, coord=False):
         """consumes self.dF (G, c_out) = dLoss/d(pooled output); leaves dLoss/dfeatures in self.dfeat (point-major,
-        padded) and this call's parameter gradients in self.grad.  Train-mode BatchNorm only (batch statistics)."""
+        padded) and this call's parameter gradients in self.grad.  Train-mode BatchNorm only (batch statistics).
+        coord: also consumes self.g_new = dLoss/d(new_xyz) and leaves dLoss/dxyz in self.dxyz (see coord_backward)."""
         plan = Plan()
         r, tot = self.rows, self.tot
         fl = net.flat
-        plan.zero_multi([fl.gacc, self.bstats, self.dfeat])
+        plan.zero_multi([fl.gacc, self.bstats, self.dfeat] + ([self.dxyz, None if self.group_all else self.dctr] if coord else []))
         m1, m2, m3 = net.mats
         o1, o2, o3 = net.bn_off
 
@@ -276,6 +300,12 @@ class _StageRun(object):
         dw(0, bn_dz(m1, o1, self.Z[0], False, G=self.G[1]), m1)
         dx(bn_dz(m1, o1, self.Z[0], True, G=self.G[1]), m1, net.c_pad, epilogue=1, dfeat=_ptr(self.dfeat), feat_c=net.c_pad,
            row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]), act_c=0, grp_per_sample=self.M)
+        if coord:
+            # the three packed columns [c_pad, c_pad + 3) the scatter epilogue above skips: same dZ, same weights
+            ga = self.group_all
+            plan.call("gad_sa_coord_grad", bn_dz(m1, o1, self.Z[0], True, G=self.G[1]), fl.p_w(m1), m1.Kp, m1.n_out, net.c_pad,
+                      _ptr(r["n"]), r["cap"], _ptr(r["pt"]), None if ga else _ptr(r["grp"]), None if ga else self.ctr,
+                      None if ga else self.g_new, r["G"], self.B * self.N, self.dxyz, None if ga else self.dctr)
         plan.call("gad_grad_from_arena", fl.gacc, fl.m2p, fl.n, self.grad, 0)
         return plan
 
@@ -324,7 +354,9 @@ class _SAFunction(torch.autograd.Function):
         new_xyz, out = _run_forward(mod, net, run, xyz, features)
         ctx.run, ctx.net, ctx.key = run, net, (B, N)
         ctx.feat_grad = features.requires_grad
-        ctx.mark_non_differentiable(*([new_xyz] if new_xyz is not None else []))
+        ctx.coord = ctx.needs_input_grad[1]                    # (sa_module_forward detaches xyz unless the module's switch is on)
+        if not ctx.coord:
+            ctx.mark_non_differentiable(*([new_xyz] if new_xyz is not None else []))
         return (new_xyz if new_xyz is not None else xyz.new_zeros(0)), out
 
     @staticmethod
@@ -333,7 +365,16 @@ class _SAFunction(torch.autograd.Function):
         B, N = ctx.key
         c_out = net.mats[2].n_out
         _transpose(g_out, run.dF, B, c_out, run.M, run.M, c_out * run.M, c_out, run.M * c_out)
-        run.bwd.run()
+        g_pts = None
+        if ctx.coord:
+            plan = run.coord_backward(net)
+            if not run.group_all:
+                run.g_new.copy_(g_xyz.reshape(run.rows["G"], 3))       # (autograd hands zeros when new_xyz went unused)
+                torch.add(run.fps, run.pt0, out=run.ctr)
+            plan.run()
+            g_pts = run.dxyz.view(B, N, 3).clone()
+        else:
+            run.bwd.run()
         g_feat = None
         if ctx.feat_grad:
             g_feat = torch.empty(B, net.c_feat, N, dtype=torch.float32, device=g_out.device)
@@ -348,7 +389,7 @@ class _SAFunction(torch.autograd.Function):
             grads.append(gcopy[o:o + p.numel()].view(p.shape) if p.requires_grad else None)
         net.free[ctx.key].append(run)                          # recycled: everything handed out above is a copy
         ctx.run = None
-        return (None, None, g_feat) + tuple(grads)
+        return (None, g_pts, g_feat) + tuple(grads)
 
 
 def sa_module_forward(mod, xyz, features):
@@ -356,8 +397,11 @@ def sa_module_forward(mod, xyz, features):
     if features is None:
         raise NotImplementedError("PointnetSAModule without input features is not used by GA-DDPG")
     # xyz may arrive with requires_grad=True for bookkeeping reasons only (the reference slices it out of the tensor that
-    # carries the broadcast action channels, core/networks.py:239): it is treated as geometry, its gradient is None
-    xyz = xyz.detach()
+    # carries the broadcast action channels, core/networks.py:239): it is treated as geometry, its gradient is None -- unless
+    # the module's `coordinate_grad` switch asks for upstream's coordinate path
+    coord = bool(getattr(mod, "coordinate_grad", False)) and torch.is_grad_enabled() and xyz.requires_grad
+    if not coord:
+        xyz = xyz.detach()
     B, N, _ = xyz.shape
     dev = xyz.device
     rt = _stage_net(mod, dev)
@@ -365,11 +409,15 @@ def sa_module_forward(mod, xyz, features):
     if features.shape[1] != net.c_feat:
         raise RuntimeError("features have %d channels, module expects %d" % (features.shape[1], net.c_feat))
     params = net.flat.params
-    needs_grad = torch.is_grad_enabled() and (features.requires_grad or any(p.requires_grad for p in params))
+    needs_grad = torch.is_grad_enabled() and (coord or features.requires_grad or any(p.requires_grad for p in params))
     if needs_grad:
         if not mod.training:
             raise RuntimeError("PointnetSAModule: backward through eval-mode BatchNorm (running statistics) is not "
                                "implemented; call .train() or wrap the call in torch.no_grad()")
+        if coord and hip.deterministic():
+            raise RuntimeError("PointnetSAModule: coordinate_grad is on and xyz requires a gradient, but the deterministic mode is "
+                               "in force (option \"deterministic\" / torch.use_deterministic_algorithms): the coordinate scatter "
+                               "adds with float atomics and has no ordered form; switch one of the two off")
         new_xyz, out = _SAFunction.apply(mod, xyz, features, *params)
         return (None if new_xyz.numel() == 0 else new_xyz), out
     key = (B, N)

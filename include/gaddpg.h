@@ -64,7 +64,9 @@ int gad_abi_version(void);                 /* bumped on any signature change or 
                                             * gad_three_nn_grid_workspace_bytes, option "tnn_grid" (additive: three_nn
                                             * through the same grid); gad_backproject_depth,
                                             * gad_backproject_depth_workspace_bytes, gad_cloud_gather_affine and
-                                            * gad_point_state_pack (additive: section A.2, depth frame -> point state)  */
+                                            * gad_point_state_pack (additive: section A.2, depth frame -> point state);
+                                            * gad_sa_coord_grad (additive: section C, the coordinate columns of a
+                                            * set-abstraction stage's first-layer gradient)  */
 /* diagnostics: which kernel family the last gad_gemm_fwd / _dx / _dw / _bwd call routed to ("gemm_fwd(stream)",
  * "gemm_dx(wide)", "gemm_bwd(stream)", "gemm_dw" = generic tile kernel, ...); bench.py labels its per-kernel table
  * with it instead of restating the routing rules.                                                  */
@@ -89,7 +91,7 @@ const char* gad_last_error(void);          /* thread-local description of the la
  * W_split_t; the streaming SA1 kernels split W themselves); otherwise it runs the FP32-MFMA kernel.
  * "deterministic" [0]: 1 = every entry point either returns a result that is bit-identical whatever the launch grid, the
  * grid-rows hints, the interleaving of streams or the timing, or refuses with GAD_ERR_UNSUPPORTED (gad_gemm_fwd mode 2; a scatter
- * epilogue with more than one group or with previous-layer statistics).  The layer GEMMs take the generic 64 x 64 tile kernels
+ * epilogue with more than one group or with previous-layer statistics; gad_sa_coord_grad).  The layer GEMMs take the generic 64 x 64 tile kernels
  * only (no streaming / wide / skinny / split-bf16 family; gad_gemm_bwd = gad_gemm_dw then gad_gemm_dx); grid-rows hints are
  * ignored; per-workgroup partial sums (BatchNorm statistics, dbeta / dgamma, split dW, sums of squares) are stored into slots of
  * a grid-independent index and added by one ordered reduce (slot order, f64) into replica 0 of the statistics or into the arena
@@ -624,6 +626,38 @@ int gad_gemm_bwd(const gad_gemm_dx_args* dx, const gad_gemm_dw_args* dw, void* s
 /* the deferred reduce of a gad_gemm_bwd(dx, dw) call made with GAD_DW_REDUCE_LATER (same argument blocks); a no-op for a
  * layer gad_gemm_bwd does not fuse (its dW was reduced by that call).                                                     */
 int gad_gemm_dw_reduce(const gad_gemm_dx_args* dx, const gad_gemm_dw_args* dw, void* stream);
+
+/* Coordinate gradient of a set-abstraction stage's gathered first layer (additive under ABI 12): the three packed columns
+ * [col0, col0 + 3) = src_xyz[pt] - ctr_xyz[grp] that gad_gemm_dx's scatter epilogue (epilogue 1) skips between dfeat and daction.
+ * Upstream reaches them through grouping_operation / gather_operation's backward (pointnet2_modules.py: grouped_xyz - new_xyz
+ * enters the first 1x1 convolution, new_xyz is a gather of xyz); a caller that trains something in front of the coordinates
+ * asks for them, GA-DDPG does not.
+ *   dz      HOST pointer to the layer's gradient source exactly as its gad_gemm_dx call carries it: gmode 0 with a dense G
+ *           (rows, g_pitch) that holds the ReLU mask already (premasked, or relu == 0), z (rows, z_pitch), coefP / Q / S given
+ *           together (or all NULL: dZ = G, z is not read), row_w (NULL -> 1), c == n_out.  The bn_* block must be unset.
+ *           Anything else: GAD_ERR_NULL / GAD_ERR_SHAPE / GAD_ERR_UNSUPPORTED before any launch.
+ *   W       (n_out, Kp) packed f32 weights of the layer; col0 = its first coordinate column (= feat_c); Kp >= col0 + 3,
+ *           1 <= n_out <= 1024.  Only columns col0 .. col0 + 2 are read.
+ *   rows    n_rows static count, n_rows_dev (nullable -> n_rows) the live count on the device: rows at or beyond
+ *           min(*n_rows_dev, n_rows) are never read.  row_pt (rows) global point number; row_grp (rows) group number with
+ *           the rows of a group contiguous, or NULL for the GroupAll form (no recentring: no centroid terms).
+ *   ctr_pt  (n_groups) global point number of every group's centroid (b * N + fps index); given exactly when row_grp is.
+ *   g_new_xyz (n_groups, 3) incoming gradient of new_xyz, nullable (needs ctr_pt).
+ *   dxyz    (n_points, 3) f32, ADDED to (as dfeat is): the caller clears it.  dctr (n_groups, 3) f32 scratch, required with
+ *           row_grp: the caller clears it as well; on return it holds the per-group sums of t.
+ * Arithmetic, f32 throughout: dZ[r][c] = P[c] * G[r][c] - w[r] * fmaf(S[c], z[r][c], Q[c]) -- the expression of gad_gemm_dx /
+ * gad_gemm_dw -- then t[r][k] = sum_c dZ[r][c] * W[c * Kp + col0 + k] for k = 0..2;  dxyz[row_pt[r]][k] += t[r][k];
+ * dctr[row_grp[r]][k] += t[r][k] (summed per run of equal row_grp inside a wavefront first); then a second launch, ordered
+ * behind the first on `stream`: dxyz[ctr_pt[g]][k] += g_new_xyz[g][k] - dctr[g][k].  Every add is a float atomic (several
+ * groups may share a centroid point; a point that is its own centroid receives both terms): the sums' order, hence their last
+ * bits, vary from run to run.  A row whose point number is outside [0, n_points), a group number outside [0, n_groups) and a
+ * centroid outside [0, n_points) are skipped, never written through.
+ * n_rows == 0 or n_groups == 0: GAD_OK without a launch.  Option "deterministic": GAD_ERR_UNSUPPORTED (no ordered form).
+ * Two launches; no workspace, no host synchronisation.                                                                   */
+int gad_sa_coord_grad(const gad_dz_src* dz, const float* W, int Kp, int n_out, int col0, const int32_t* n_rows_dev,
+                      int n_rows, const int32_t* row_pt, const int32_t* row_grp /*nullable*/,
+                      const int32_t* ctr_pt /*nullable*/, const float* g_new_xyz /*nullable*/, int n_groups, int n_points,
+                      float* dxyz, float* dctr /*nullable*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * D. heads' losses (forward value + gradient wrt head outputs in one pass)
