@@ -103,7 +103,7 @@ class Agent(object):
         geometry of both cloud sets -- of the one a BC agent has -- on the prefetch lanes): the following
         update_parameters(batch_data) -- the same object -- starts from there.  A hint: results never depend on it;
         device-resident minibatches only.  -> True if the hint will be used, False otherwise (host batches, no runtime yet,
-        the call-by-call enqueue, a data-parallel BC run)."""
+        a step whose launch list is walked from Python instead of replayed, such as a data-parallel BC run)."""
         if self._rt is None or batch_data is None:
             return False
         return bool(self._rt.prefetch_inputs(batch_data))

@@ -733,7 +733,8 @@ class Plan(object):
     `side=k` run on weight-gradient lane k (= logical stream 10 + k) between a fork (the lane waits for everything recorded so
     far on the main stream) and the next join (main waits for the lane): the weight-gradient GEMMs are off the dX critical path.
     run() replays the list through gad_plan_run (include/gaddpg.h section H: one foreign call per plan, or per segment between
-    host callbacks); the item-by-item Python walk remains for the serialised / timing-probe diagnostics."""
+    host callbacks); run(walk=True) / run_py() walks the same items one by one from Python: the timing probes, GAD_PLAN_C=0 and
+    the update steps that runtime.FusedRuntime._replays() does not replay."""
 
     def __init__(self):
         self.calls = []      # _Items
@@ -862,10 +863,11 @@ class Plan(object):
                 hip.check(L.gad_plan_patch(h, i, index, C.c_uint64(word)), "gad_plan_patch")
 
     # ---- replay -------------------------------------------------------------------------------------------------------
-    def run(self):
+    def run(self, walk=False):
+        """replay the list in C; walk=True (or GAD_PLAN_C=0, or a timing probe that still has to learn a route): run_py()"""
         hip.sync_deterministic()           # (torch.use_deterministic_algorithms may have changed since the last call)
         timed = TIMING["enabled"]
-        if not USE_C_PLANS or (timed and any(it.tag is not None and it.name in _TIMED_CALLS and it.tag not in _ROUTES
+        if walk or not USE_C_PLANS or (timed and any(it.tag is not None and it.name in _TIMED_CALLS and it.tag not in _ROUTES
                                               for it in self.calls)):
             return self.run_py()
         import ctypes as C

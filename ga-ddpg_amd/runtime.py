@@ -6,6 +6,11 @@ critic phase (extract_feature -> target_value -> compute_critic_loss -> critic_o
 actor phase (extract_feature -> policy.sample -> [actor-critic term every policy_update_gap
 steps] -> compute_loss -> optimize -> target updates) and BC.update_parameters (core/bc.py:71-87).
 Host <-> device traffic per step: one pinned upload of the minibatch, one 32-float download.
+
+Each step kind is described ONCE, as an engine.Plan (_build_step_plan / _build_bc_plan, with the prefetch lanes in
+_prefetch_plan).  The list is replayed in C (gad_plan_run) when _replays() holds; otherwise -- GAD_STEP_PLAN=0, the separate
+optimiser launches, update_parameters(test=True), a one-stream or data-parallel BC step -- the same list is walked item by
+item from Python (Plan.run(walk=True)).
 """
 import numpy as np
 import torch
@@ -17,17 +22,12 @@ BATCH_KEYS = ("point_state_batch", "next_point_state_batch", "action_batch", "ex
               "return_batch", "mask_batch", "time_batch", "goal_batch", "expert_flag_batch", "perturb_flag_batch")
 
 
-OVERLAP_PASSES = True      # run independent encoder passes of the DDPG step on side streams
 import os as _os
-# (measured and removed, same box, 287-288 steps/s for the schedule below: HIP-graph replay of the step 240; the actor pass
-# started beside t1 272; the next step's value pass under this step's actor backward: no gain; the actor pass after t2, i.e.
-# beside the critic backward only: 275; the value pass after t1, beside t2 and the actor pass: 282; both side passes
-# swapped: 278 -- profiles/README.md round 2)
 ROW_HINTS = _os.environ.get("GAD_ROW_HINTS", "1") == "1"     # grids of the SA1 / SA2 tile launches sized for the expected live rows
 EARLY_ZERO = _os.environ.get("GAD_EARLY_ZERO", "1") == "1"   # backward buffers cleared at the end of the forward plans; t2's running update on the value stream
 INPUT_SETS = int(_os.environ.get("GAD_INPUT_SETS", "2"))      # 1: uploads + geometry in front of every step (round-1 schedule)
 STEP_PLAN = _os.environ.get("GAD_STEP_PLAN", "1") == "1"      # the whole update step as ONE replayed launch list (FusedRuntime._step_plan);
-                                                              # 0: enqueued call by call from Python (_ddpg_enqueue: the same launches)
+                                                              # 0: the same list walked item by item from Python (Plan.run_py)
 # BC only, A/B: prefetch_inputs() enqueues the staging at once (into the set the step after the coming one uses) instead of behind
 # the coming step's launches.  OFF: measured +1 - 3 % over no prefetch where the deferred order gives +12 %
 # (profiles/bc_pipeline.txt), and it only pays for a caller that hints before it updates
@@ -142,8 +142,7 @@ class FusedRuntime(object):
                                    slot_t=engine.slot_view(self.slot_t, geon2) if self.has_critic else None))
         for st in self._sets:
             st["rows_pin"] = torch.zeros(4, dtype=torch.int32).pin_memory()    # live rows of [geo SA1, SA2, geo_next SA1, SA2]
-            st.update(ev_in=torch.cuda.Event(), ev_gn=torch.cuda.Event(), ev_g=torch.cuda.Event(), ev_up=torch.cuda.Event(), ev_free=None,
-                      plans=None)
+            st.update(ev_up=torch.cuda.Event(), ev_free=None, plans=None)
         self._set = 0
         self._rows_seen = [[], []]            # recent live-row counts of SA1 / SA2 (grid-size hints, engine.Geometry.rows_hint)
         self.scal = torch.zeros(64, **f32)          # [0, 32): the step's result block; [32, 56): 3 x 8 spread max-abs slots
@@ -179,11 +178,9 @@ class FusedRuntime(object):
         self.world_size = 1
         self.inv_n = None
         self.resident = False            # True: the static batch buffers were filled on the device
-        self._ev = [torch.cuda.Event() for _ in range(5)]
-        self._ev_counts = torch.cuda.Event()
-        self._ev_in = torch.cuda.Event()
+        self._ev_noise = torch.cuda.Event()
         self._ev_pre = torch.cuda.Event()
-        self._ev_run = torch.cuda.Event()
+        self._eval = False               # True while an update_parameters(test=True) step is enqueued
         self.noise_host = self._noise_ring[0]
 
     # ------------------------------------------------------------------ plans over static buffers
@@ -293,7 +290,7 @@ class FusedRuntime(object):
         t1 = engine.plan_encoder_forward(enc, self.slot_t, action=None, train=train)
         t1.extend(heads.plan_policy_forward(self.pol_t, self.hs_pt, enc, self.slot_t, d["time_m1"]))
         t1.call("gad_policy_outputs", self.hs_pt.out, self.B, self.pol_t.n_heads, self.action_scale, self.action_bias, self.pi_t, None)
-        t2 = engine.plan_encoder_forward(venc, self.slot_t, action=self.a_next, update_running=not OVERLAP_PASSES, train=train)
+        t2 = engine.plan_encoder_forward(venc, self.slot_t, action=self.a_next, update_running=False, train=train)
         P["t2_run"] = engine.plan_running_update(venc, self.slot_t)
         t2.extend(heads.plan_critic_forward(self.cr_t, self.hs_ct, venc, self.slot_t, d["time_m1"]))
         P["c_fwd"], P["t1"], P["t2"] = c, t1, t2
@@ -434,7 +431,7 @@ class FusedRuntime(object):
         ag = self.agent
         jobs = self._optim_jobs()
         fold = self.dp is None                # (data-parallel runs keep the separate launch: their phases end with exchanges)
-        ev = getattr(self, "_eval", False)    # eval-mode BatchNorm (test=True): num_batches_tracked stays
+        ev = self._eval                       # eval-mode BatchNorm (test=True): num_batches_tracked stays
         if which == "end":
             if fold:
                 return None                   # (folded: see above)
@@ -453,30 +450,33 @@ class FusedRuntime(object):
                 js[2].counter_add = 0 if ev else 3
         return js
 
-    def _optim_phase(self, which, policy_step):
-        """gad_optim_jobs for the critic phase ("c"), the actor phase ("a") or the end of the step ("end": what has to
-        wait for both phases -- max |critic.grad| as the reference logs it after the actor backward, the value encoder's
-        BatchNorm counters)"""
-        ag = self.agent
-        js = self._optim_select(which, policy_step)
-        if js is None:
-            return
-        hip.check(hip.lib().gad_optim_jobs(js, len(js), hip.stream()), "gad_optim_jobs")
-        if which == "c":                     # the encoders' split-bf16 weight mirrors follow their packed weights
-            self.venc.flat.refresh_split()
-        elif which == "a" and ag.train_feature:
-            self.enc.flat.refresh_split()
-
     def _adam_host(self, flat, optim):
         g = optim.param_groups[0]
         flat.set_adam_hyper(g["lr"], g["betas"], g["eps"], g["weight_decay"], upload=False)
 
-    def _adam(self, flat, optim, clip=None):
-        self._adam_host(flat, optim)
-        flat.hyper.copy_(flat.hyper_host, non_blocking=True)
+    def _adam(self, flat, clip=None):
+        """one network's Adam step as a launch of its own (its scalars: _adam_host + the step's one upload of the block)"""
         hip.call("gad_adam_step", flat.master, flat.grad, flat.exp_avg, flat.exp_avg_sq, flat.active, flat.m2p,
                  flat.packed, flat.n, flat.hyper, clip, float(self.agent.clip_grad) if clip is not None else 0.0)
         flat.refresh_split()
+
+    def _unfused_optim(self, which, policy_step):
+        """optimiser phase `which` (_plan_optim) as separate launches on the current stream; a host callback of the step's list:
+        train_feature and the target-update interval are read when the step is enqueued, like the Adam scalars"""
+        if which == "c":
+            self._adam(self.venc.flat)
+            self._adam(self.cr.flat, clip=self.clip_sumsq)
+        elif which == "a":
+            self._adam(self.pol.flat)
+            if self.agent.train_feature:
+                self._adam(self.enc.flat)
+        else:
+            self._target_updates()
+            self._stats()
+            if not self._eval:                 # (eval-mode BatchNorm: num_batches_tracked stays)
+                self.enc.bump_batches_tracked(2 if self.has_critic else 1)      # policy-encoder passes of the step: DDPG two, BC one
+                if self.has_critic:
+                    self.venc.bump_batches_tracked(3 if policy_step else 2)
 
     def _reduce(self, flats, tag=None):
         if self.allreduce is None:
@@ -537,14 +537,18 @@ class FusedRuntime(object):
                     if st["geo_next"] is not None:
                         st["geo_next"].rows_hint[stage] = h
 
-    def _end_step(self, slot, sync, fused=None):
-        """fused: the step's optimiser phases ran as gad_optim_jobs launches (default: self.fused_optim)"""
+    def _fused(self):
+        """True: the step's optimiser phases are gad_optim_jobs launches; False: the separate Adam / target / statistics launches
+        (set_fused_optim(False); a data-parallel BC run keeps them too)"""
+        return self.fused_optim and (self.has_critic or self.dp is None)
+
+    def _end_step(self, slot, sync):
         ev = self._ev_done[slot]
         if ev is None:
             ev = self._ev_done[slot] = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         self._sets[self._set]["ev_free"] = ev        # every stream of the step has been joined into this one by now
-        fused = self.fused_optim if fused is None else fused
+        fused = self._fused()
         if sync:
             ev.synchronize()
             return _fold_stats(self.scal_host.numpy(), fused)
@@ -559,54 +563,45 @@ class FusedRuntime(object):
         torch.cuda.current_stream().synchronize()
 
     def _replays(self):
-        """True: the update step runs as ONE replayed launch list (_step_plan); False: enqueued call by call from Python"""
+        """True: the update step's launch list (_step_plan) is replayed in C; False: the same list is walked item by item from Python"""
         if self.has_critic:
-            return STEP_PLAN and OVERLAP_PASSES and self.fused_optim
-        # BC: one stream of launches anyway; a data-parallel BC run and the one-stream diagnostic keep the call-by-call enqueue
+            return STEP_PLAN and self.fused_optim
+        # BC: one stream of launches anyway; a data-parallel BC run and the one-stream diagnostic are walked
         return STEP_PLAN and self.fused_optim and self.dp is None and not engine.SERIAL
 
-    def _finish_step(self, slot, sync, replay, fused=None):
+    def _finish_step(self, slot, sync, replay):
         """close a step; a minibatch handed to prefetch_inputs() meanwhile is staged behind the step's own launches, before the
         host waits for its result"""
         nxt, self._next_batch = getattr(self, "_next_batch", None), None
         if nxt is not None and replay:
-            pend = self._end_step(slot, False, fused)
+            pend = self._end_step(slot, False)
             self._prefetch_now(nxt)
             if not sync:
                 return pend
             v = pend.wait()
             self._pending[slot] = None
             return v
-        return self._end_step(slot, sync, fused)
+        return self._end_step(slot, sync)
 
     def ddpg_step(self, batch, noise_u=None, sync=True, test=False):
-        """one DDPG / TD3 update: eager multi-stream enqueue.
+        """one DDPG / TD3 update: its multi-stream launch list, replayed or walked.
         sync=False: return a PendingStep right after the enqueue.  The host then prepares and enqueues the next step while
         this one runs (up to engine.HOST_RING - 1 steps ahead): the ~2 ms of launch calls, the uploads and the geometry of
-        step N+1 no longer sit in front of its critical chain, they are queued behind step N on the GPU."""
+        step N+1 no longer sit in front of its critical chain, they are queued behind step N on the GPU.
+        test=True (reference core/agent.py:276-280): the same update with eval-mode BatchNorm in every pass -- a list of its own over
+        _eval_plans(), always walked (no shipped configuration trains this way: not a fast path)"""
         ag = self.agent
         policy_step = ag.update_step % ag.policy_update_gap == 0
         slot = self._begin_step(alternate=True)
-        self._eval = bool(test)
         replay = (not test) and self._replays()
-        if not replay:
-            self._sets[self._set]["prefetched"] = None        # (the call-by-call path stages its inputs itself)
-        if test:
-            # test=True (reference core/agent.py:276-280): the same update with eval-mode BatchNorm in every pass -- its own plans,
-            # enqueued call by call (no shipped configuration trains this way: not a replayed list, not a fast path)
-            keep = self.plans
-            self.plans = self._eval_plans()
-            try:
-                self._ddpg_enqueue(batch, noise_u, policy_step)
-            finally:
-                self.plans, self._eval = keep, False
-        elif replay:
-            self._ddpg_replay(batch, noise_u, policy_step)
-        else:
-            self._ddpg_enqueue(batch, noise_u, policy_step)
+        self._eval = bool(test)
+        try:
+            self._ddpg_run_list(batch, noise_u, policy_step, walk=not replay)
+        finally:
+            self._eval = False
         return self._finish_step(slot, sync, replay)
 
-    # ------------------------------------------------------------------ the step as ONE replayed launch list
+    # ------------------------------------------------------------------ the step as ONE launch list
     def _step_key(self):
         ag = self.agent
         self._optim_jobs()
@@ -615,27 +610,30 @@ class FusedRuntime(object):
                 self.bucketed, ROW_HINTS, EARLY_ZERO, hip.sync_deterministic())
 
     def _step_plan(self, set_index, policy_step):
-        """The whole update step over input / geometry set `set_index` as one engine.Plan (what _ddpg_enqueue issues call by
-        call, in the same order on the same logical streams): replayed by gad_plan_run in one foreign call -- or a few, when a
-        data-parallel run has host callbacks (collectives) inside the step.  What changes from step to step is patched into
-        the list before the run (_ddpg_replay): the noise level, the mix ratio, the pinned ring slot of the Adam scalars and
-        of the result block; the optimiser scalars live in the job arrays the list points to."""
+        """The whole update step over input / geometry set `set_index` as one engine.Plan, the only description of the step:
+        replayed by gad_plan_run in one foreign call -- or a few, when host callbacks (a data-parallel run's collectives, the
+        separate optimiser launches) sit inside the step -- or walked item by item.  What changes from step to step is patched
+        into the list before the run (_ddpg_run_list): the noise level, the mix ratio, the pinned ring slot of the Adam
+        scalars and of the result block; the optimiser scalars live in the job arrays the list points to.  An eval-mode step
+        (self._eval) has a list of its own, over _eval_plans()."""
         key = self._step_key()
         cache = self.__dict__.setdefault("_step_plans", {})
         if cache.get("key") != key:
             cache.clear()
             cache["key"] = key
             cache["refs"] = (self.dp, self.allreduce, self.inv_n)      # (alive while their ids are part of the key)
-        ent = cache.get((set_index, policy_step))
+        ent = cache.get((set_index, policy_step, self._eval))
         if ent is not None:
             return ent
         bound = self._set
         st = self._bind_set(set_index)
         try:
+            if self._eval:
+                self.plans = self._eval_plans()
             ent = self._build_step_plan(st, policy_step)
         finally:
             self._bind_set(bound)
-        cache[(set_index, policy_step)] = ent
+        cache[(set_index, policy_step, self._eval)] = ent
         return ent
 
     def _prefetch_plan(self, st):
@@ -673,6 +671,13 @@ class FusedRuntime(object):
         return pre
 
     def _build_step_plan(self, st, policy_step):
+        """The DDPG step over the bound set (a BC runtime: _build_bc_plan) on four lanes: MAIN = the caller's stream, the TD-target
+        chain and the critic phase; S1 = the value pass of the current state; S2 = the actor pass; SC = small initialisations.
+        Measured and rejected, same box, against 287-288 steps/s for this schedule: HIP-graph replay of the step 240; the actor
+        pass started beside t1 272; the next step's value pass under this step's actor backward: no gain; the actor pass after
+        t2, i.e. beside the critic backward only: 275; the value pass after t1, beside t2 and the actor pass: 282; both side
+        passes swapped: 278 (profiles/README.md round 2); the end-of-step bookkeeping on SC instead of MAIN: 287 vs 297 -- that
+        lane's queue also carries the next step's uploads and geometry."""
         ag, d, P = self.agent, self.dbuf, self.plans
         B = self.B
         EH = engine.EventHolder
@@ -685,10 +690,20 @@ class FusedRuntime(object):
         M.keep.append((ev0, ev1, ev2, ev3, ev4, ev_run, ev_counts, pre))
         if not self.has_critic:
             return self._build_bc_plan(M, H, Mpre, ev_g)
-        # ---- critic phase (the comments of _ddpg_enqueue apply line by line)
+        # ---- critic phase.  The TD target chain (encoder(next) -> target policy -> value encoder(next, a') -> target critic)
+        # and the value pass on the current state are independent: the latter runs on S1.  Both go through value_encoder's
+        # BatchNorms; the reference runs the current-state pass first (core/ddpg.py:145-152, then target_value() inside
+        # compute_critic_loss), so the target chain's value-encoder pass only computes batch statistics and its
+        # running-statistics momentum update (t2_run) is applied after the join.
+        # The side lanes share weights and activation scratch with the previous step: they start after it (ev0 on MAIN, which
+        # every lane of that step was joined into) and after their inputs on the prefetch lanes (ev_gn: the next state's
+        # geometry; ev_g: ALL inputs + the current state's geometry).
         M.record(ev0, on=MAIN)
         M.wait_event(ev_gn, on=MAIN)
-        M.extend(P["t1"], on=MAIN)
+        M.extend(P["t1"], on=MAIN)                # FIRST in the list: a walking host needs ~0.1 ms for the launches below
+        # small independent launches (result-slot clear, the Adam scalars' upload, and for data-parallel runs the global mask
+        # counts: a 4-double all-reduce) would sit on the critical chain in front of t1: on SC they overlap the geometry and t1;
+        # MAIN -- and through ev2 the actor lane -- waits for them after t1
         M.wait_event(ev0, on=SC)
         M.wait_event(ev_g, on=SC)
         M.zero(self.scal, on=SC)
@@ -700,7 +715,14 @@ class FusedRuntime(object):
         M.wait_event(ev0, on=S1)
         M.wait_event(ev_g, on=S1)
         M.extend(P["c_fwd"], on=S1)
+        # The actor phase's policy forward needs nothing from the critic update: it starts as soon as t1 is done (ev2; its encoder
+        # BatchNorms must come after t1's, as in the reference) and runs beside t2 and the critic backward.  On steps without
+        # the actor-critic term (update_step % policy_update_gap != 0) the WHOLE actor phase -- loss, backward, Adam of policy +
+        # encoder -- is independent of the critic phase (disjoint parameters, gradient arenas, dW lanes and result slots) and
+        # runs there too.
         M.record(ev2, on=MAIN)
+        # the rest of the target chain comes BEFORE the actor pass: a walking host needs ~0.4 ms for the actor pass's launches,
+        # and MAIN (the critical path) would sit idle behind them
         H["noise"] = M.call("gad_target_noise", self.pi_t, self.noise_u, B, 0.0, 0, self.a_next, on=MAIN)
         M.extend(P["t2"], on=MAIN)
 
@@ -719,10 +741,14 @@ class FusedRuntime(object):
             actor_tail(None, S2)
         M.record(ev1, on=S1)
         M.wait_event(ev1, on=MAIN)
+        # the target chain's deferred running-statistics update: on the value lane, behind the value pass's own updates (the
+        # reference's order) and the target pass (ev4), off MAIN's chain; MAIN picks it up again (ev_run, long done by then)
+        # before the next writer of those statistics.  Eval-mode BatchNorm: the running statistics stay
         M.record(ev4, on=MAIN)
         M.wait_event(ev4, on=S1)
         lane_run = S1 if EARLY_ZERO else MAIN
-        M.extend(P["t2_run"], on=lane_run)
+        if not self._eval:
+            M.extend(P["t2_run"], on=lane_run)
         M.record(ev_run, on=lane_run)
         M.call("gad_critic_loss", self.hs_c.out, self.hs_ct.out, d["reward_batch"], d["mask_batch"], d["perturb_flag_batch"],
                d["return_batch"], d["goal_batch"], B, float(ag.gamma), int(bool(ag.critic_aux)), self.inv_n_critic(), self.y,
@@ -731,7 +757,7 @@ class FusedRuntime(object):
         M.wait_event(ev_run, on=MAIN)
         if self.allreduce is not None:
             M.fn(lambda: self._reduce([self.cr.flat, self.venc.flat], "c"), on=MAIN)
-        if self.dp is not None:
+        if self.dp is not None or not self._fused():      # (otherwise the backward plan's conversion launch formed the sum of squares)
             M.call("gad_sumsq", self.cr.flat.grad, self.cr.flat.n, self.clip_sumsq, on=MAIN)
         optim("c", MAIN)
         # ---- actor phase
@@ -767,6 +793,13 @@ class FusedRuntime(object):
         self._plan_optim(M, policy_step, "a", on)
 
     def _plan_optim(self, M, policy_step, which, on):
+        """the optimiser launch of the critic phase ("c"), the actor phase ("a") or the end of the step ("end": what has to wait
+        for both phases -- max |critic.grad| as the reference logs it after the actor backward, the value encoder's BatchNorm
+        counters; folded into one of the other two outside data-parallel runs) and the split-bf16 weight mirror that follows
+        the encoder's packed weights"""
+        if not self._fused():
+            M.fn(lambda: self._unfused_optim(which, policy_step), on=on)
+            return
         js = self._optim_select(which, policy_step)
         if js is None:
             return
@@ -780,21 +813,28 @@ class FusedRuntime(object):
         ONE upload of the Adam scalars, policy forward -> outputs -> cloning loss (coefficient 1, no critic term) -> backward ->
         ONE optimiser launch (policy: arena -> grad, Adam, policy_target, max |parameter|; encoder: Adam when it trains,
         num_batches_tracked + 1) -> the encoder's split-bf16 mirror -> result block to the pinned ring slot.  The two small
-        items in front do not need the inputs: they run before the list waits for the prefetch lane's geometry."""
+        items in front do not need the inputs: they run before the list waits for the prefetch lane's geometry.
+        Not fused (_fused(): set_fused_optim(False), a data-parallel run): host callbacks make the separate Adam / target /
+        statistics launches instead; a data-parallel run adds its collectives (mask counts, gradients, result block)."""
         MAIN = 0
         M.zero(self.scal, on=MAIN)
         H["hyper"] = M.memcpy(self.hyper_all.data_ptr(), self._hyper_ring[0].data_ptr(), 4 * self.hyper_all.numel(), on=MAIN)
         M.wait_event(ev_g, on=MAIN)
+        if self.dp is not None:
+            M.fn(lambda: self.dp.set_counts(self._cur_batch), on=MAIN)
         M.extend(self.plans["p_fwd"], on=MAIN)
         self._plan_policy_outputs(M, MAIN)
         self._plan_actor_tail(M, H, False, None, MAIN, coef=1.0)
+        self._plan_optim(M, False, "end", MAIN)          # (fused: nothing, the actor phase's launch carries it)
+        if self.dp is not None:
+            M.fn(lambda: self.dp.reduce_scalars(self.scal), on=MAIN)
         H["download"] = M.memcpy(self._scal_ring[0].data_ptr(), self.scal.data_ptr(), 4 * self.scal.numel(), on=MAIN)
         return dict(plan=M, pre=Mpre, items=H, last={})
 
-    def _stage_inputs(self, batch, st, pre):
+    def _stage_inputs(self, batch, st, pre, walk=False):
         """the inputs of a step into set `st` + its prefetch list `pre` (geometry of both cloud sets; BC: of the one): stream
         waits on events owned by other steps / producers, the uploads (or the one gather / copy launch of a device-resident
-        minibatch), then the replayed prefetch-lane launches.  The set must be the bound one (self.dbuf / self.geo*)."""
+        minibatch), then the prefetch-lane launches, replayed or (walk) walked.  The set must be the bound one (self.dbuf / self.geo*)."""
         main = torch.cuda.current_stream()
         spre2 = engine.side_stream(which=21)
         spre = engine.side_stream(which=20) if self.has_critic else spre2       # (BC: one lane, there is no next-state chain)
@@ -817,7 +857,7 @@ class FusedRuntime(object):
                 self.upload(batch, tuple(k for k in BATCH_KEYS if k not in first))
         if isinstance(batch, dict) and "uploaded_event" in batch:   # asked for by the producer (PrefetchSampler): it may
             batch["uploaded_event"] = st["ev_up"]                   # reuse its staging buffers after this event
-        pre.run()
+        pre.run(walk=walk)
 
     def prefetch_inputs(self, batch):
         """Stage the NEXT step's minibatch now: its upload (one gather / copy launch) and the geometry of both cloud sets go onto
@@ -854,19 +894,20 @@ class FusedRuntime(object):
             self._bind_set(bound)
         return True
 
-    def _ddpg_replay(self, batch, noise_u, policy_step):
-        """enqueue one update step through its replayed launch list (_step_plan).  Eager host work that remains: the staging of
-        the inputs (unless prefetch_inputs did it), the TD3 noise draw from torch's generator, this step's scalars."""
+    def _ddpg_run_list(self, batch, noise_u, policy_step, walk):
+        """enqueue one update step through its launch list (_step_plan), replayed in C or (walk) item by item from Python; no host
+        synchronisation inside.  Eager host work that remains: the staging of the inputs (unless prefetch_inputs did it), the
+        TD3 noise draw from torch's generator, this step's scalars."""
         ag = self.agent
         st = self._sets[self._set]
         ent = self._step_plan(self._set, policy_step)
         self._cur_batch = batch
         main = torch.cuda.current_stream()
         sc = engine.side_stream(which=3)
-        self._take_inputs(batch, st, ent)
+        self._take_inputs(batch, st, ent, walk)
         # the TD3 noise: torch's device generator (or the injected draw), ordered after the previous step's reader
-        self._ev[0].record(main)
-        sc.wait_event(self._ev[0])
+        self._ev_noise.record(main)
+        sc.wait_event(self._ev_noise)
         normal_noise = getattr(ag, "noise_type", "uniform") != "uniform"     # core/utils.py:568-569
         with torch.cuda.stream(sc):
             if noise_u is None:
@@ -888,21 +929,22 @@ class FusedRuntime(object):
         level = float(ag.action_noise * ag.noise_ratio_list[min(len(ag.noise_ratio_list) - 1, idx)])
         ratio = float(ag.mix_policy_ratio)
         self._patch_and_run(ent, {("noise", 3): level, ("noise", 4): int(normal_noise), ("actor_loss", 8): 1.0 - ratio,
-                                  ("ac_loss", 4): ratio})
+                                  ("ac_loss", 4): ratio}, walk)
         self._cur_batch = None
 
-    def _take_inputs(self, batch, st, ent):
-        """the step's inputs: staged now, unless prefetch_inputs() staged this very batch object into the set already"""
+    def _take_inputs(self, batch, st, ent, walk):
+        """the step's inputs: staged now, unless prefetch_inputs() staged this very batch object into the set already (a walked
+        step always stages its own, in front of its launches: prefetch_inputs() defers nothing to it)"""
         engine.apply_lane_priorities(torch.cuda.current_stream())
         staged, st["prefetched"] = st.get("prefetched"), None
-        if staged is None or staged is not batch:
-            self._stage_inputs(batch, st, ent["pre"])
+        if walk or staged is None or staged is not batch:
+            self._stage_inputs(batch, st, ent["pre"], walk)
         elif isinstance(batch, dict) and "uploaded_event" in batch:
             batch["uploaded_event"] = st["ev_up"]
 
-    def _patch_and_run(self, ent, want):
+    def _patch_and_run(self, ent, want, walk):
         """write what changed since the list last ran into it -- `want` {(item, argument index): value} plus the pinned ring slot
-        of the Adam scalars and of the result block -- and replay it"""
+        of the Adam scalars and of the result block -- and replay or walk it (Plan.patch reaches both forms)"""
         H, last = ent["items"], ent["last"]
         want[("hyper", 1)] = self._hyper_ring[self._slot].data_ptr()
         want[("download", 0)] = self.scal_host.data_ptr()
@@ -910,276 +952,31 @@ class FusedRuntime(object):
             if name in H and last.get((name, index)) != v:
                 Plan.patch(H[name], index, v)
                 last[(name, index)] = v
-        ent["plan"].run()
+        ent["plan"].run(walk=walk)
 
-    def _bc_replay(self, batch):
-        """enqueue one BC update through its replayed launch list (_build_bc_plan).  Eager host work that remains: the staging of
-        the inputs (unless prefetch_inputs did it) and this step's Adam scalars, read from the torch optimisers now."""
+    def _bc_run_list(self, batch, walk):
+        """enqueue one BC update through its launch list (_build_bc_plan), replayed or walked.  Eager host work that remains: the
+        staging of the inputs (unless prefetch_inputs did it) and this step's Adam scalars, read from the torch optimisers now."""
         ag = self.agent
         st = self._sets[self._set]
         ent = self._step_plan(self._set, False)
-        self._take_inputs(batch, st, ent)
+        self._cur_batch = batch
+        self._take_inputs(batch, st, ent, walk)
         self._adam_host(self.pol.flat, ag.policy_optim)
         if ag.train_feature:
             self._adam_host(self.enc.flat, ag.state_feat_encoder_optim)
         self._optim_select("a", False)
-        self._patch_and_run(ent, {})
-
-    def _ddpg_enqueue(self, batch, noise_u, policy_step):
-        """enqueue one update step on the current stream + the side streams (no host synchronisation inside); ends with the
-        32-float result block on its way to the pinned host buffer"""
-        ag, d, P = self.agent, self.dbuf, self.plans
-        B = self.B
-        ratio = float(ag.mix_policy_ratio)
-        main = torch.cuda.current_stream()
-        # uploads + geometry of both cloud sets on the prefetch stream, into this step's input / geometry set: ordered only
-        # after the last step that used the set, i.e. they run beside the previous step when the host is ahead of the GPU
-        st = self._sets[self._set]
-        inline = (not OVERLAP_PASSES) or engine.serial()
-        spre = main if inline else engine.side_stream(which=20)
-        spre2 = main if inline else engine.side_stream(which=21)
-        if not inline:
-            ready = batch.get("ready_event") if batch is not None else None
-            if ready is None and batch is not None and ("replay_gather" in batch or (
-                    torch.is_tensor(batch["point_state_batch"]) and batch["point_state_batch"].is_cuda)):
-                self._ev_pre.record(main)               # device tensors of unknown origin: after everything enqueued so far
-                ready = self._ev_pre
-            for s_ in (spre, spre2):
-                if st["ev_free"] is not None:
-                    s_.wait_event(st["ev_free"])
-                if ready is not None:                   # (a producer's event says when its device tensors are complete)
-                    s_.wait_event(ready)
-        # two prefetch streams: [inputs of the target chain -> geometry of the next state] and [the rest -> geometry of the
-        # current state] run side by side (each geometry is a chain of small latency-bound kernels)
-        whole = batch is not None and "replay_gather" in batch          # one gather launch fills every buffer
-        first = ("next_point_state_batch", "time_batch")
-        with torch.cuda.stream(spre):
-            self.upload(batch, None if whole else first)
-            st["ev_in"].record(spre)
-            self.geo_next.run(d["next_point_state_batch"])      # the target chain (the critical path) needs this one first
-            st["ev_gn"].record(spre)
-            if ROW_HINTS:
-                st["rows_pin"][2:3].copy_(self.geo_next.rows[0]["n"], non_blocking=True)
-                st["rows_pin"][3:4].copy_(self.geo_next.rows[1]["n"], non_blocking=True)
-        if whole and not inline:
-            spre2.wait_event(st["ev_in"])
-        with torch.cuda.stream(spre2):
-            if not whole:
-                self.upload(batch, tuple(k for k in BATCH_KEYS if k not in first))
-                if not inline:
-                    spre2.wait_event(st["ev_in"])
-            st["ev_up"].record(spre2)                           # every input of the step has left the caller's buffers
-            self.geo.run(d["point_state_batch"])
-            st["ev_g"].record(spre2)                            # ev_g: ALL inputs are in + the geometry of the current state
-            if ROW_HINTS:
-                st["rows_pin"][0:1].copy_(self.geo.rows[0]["n"], non_blocking=True)
-                st["rows_pin"][1:2].copy_(self.geo.rows[1]["n"], non_blocking=True)
-        if isinstance(batch, dict) and "uploaded_event" in batch:   # asked for by the producer (PrefetchSampler): it may
-            batch["uploaded_event"] = st["ev_up"]                   # reuse its staging buffers after this event
-        idx = sum(1 for m in ag.mix_milestones if ag.update_step > m)
-        level = ag.action_noise * ag.noise_ratio_list[min(len(ag.noise_ratio_list) - 1, idx)]
-        normal_noise = getattr(ag, "noise_type", "uniform") != "uniform"     # core/utils.py:568-569
-
-        def small_inits():
-            # not needed by the geometry / first passes: enqueued after them so that the GPU starts the step earlier
-            if noise_u is None:
-                if normal_noise:
-                    self.noise_u.normal_()                              # torch.randn_like (core/utils.py:573)
-                else:
-                    self.noise_u.uniform_(0.0, 1.0)                     # torch.rand_like (core/utils.py:575)
-            else:
-                self.noise_u.copy_(torch.as_tensor(np.asarray(noise_u, dtype=np.float32)), non_blocking=True)
-            self.scal.zero_()
-            if self.fused_optim:                    # this step's Adam scalars of all four networks: one upload
-                self._adam_host(self.venc.flat, ag.state_feat_val_encoder_optim)
-                self._adam_host(self.cr.flat, ag.critic_optim)
-                self._adam_host(self.pol.flat, ag.policy_optim)
-                if ag.train_feature:
-                    self._adam_host(self.enc.flat, ag.state_feat_encoder_optim)
-                self.hyper_all.copy_(self._hyper_ring[self._slot], non_blocking=True)
-        # ---- critic phase.  The TD target chain (encoder(next) -> target policy -> value encoder(next, a') -> target
-        # critic) and the value pass on the current state are independent: the latter runs on a second stream.
-        # Both go through value_encoder's BatchNorms; the reference runs the current-state pass first
-        # (core/ddpg.py:145-152, then target_value() inside compute_critic_loss), so the target chain's value-encoder
-        # pass only computes batch statistics and its running-statistics momentum update is applied after the join.
-        def actor_tail(g_pi):
-            hip.call("gad_actor_loss", self.hs_p.out, self.pi, d["expert_action_batch"], d["expert_flag_batch"],
-                     d["return_batch"], d["goal_batch"], B, self.pol.n_heads, 1.0 - ratio, int(bool(ag.policy_aux)),
-                     self.action_scale, g_pi,
-                     self.inv_n_actor(), self.hs_p.g_out, engine._ptr(self.scal, 4))
-            P["p_bwd"].run()
-            if self.fused_optim:
-                self._reduce([self.pol.flat, self.enc.flat], "a")          # (no-op outside data-parallel runs)
-                self._optim_phase("a", policy_step)
-                return
-            self._reduce([self.pol.flat, self.enc.flat], "a")
-            self._adam(self.pol.flat, ag.policy_optim)
-            if ag.train_feature:
-                self._adam(self.enc.flat, ag.state_feat_encoder_optim)
-
-        if OVERLAP_PASSES:
-            s1, s2, sc = engine.side_stream(which=1), engine.side_stream(which=2), engine.side_stream(which=3)
-            engine.apply_lane_priorities(main)
-            # the side streams share weights and activation scratch with the previous step: they start after it (ev[0] on the
-            # main stream, which every stream of that step was joined into) and after their inputs on the prefetch stream
-            self._ev[0].record(main)
-            main.wait_event(st["ev_gn"])
-            P["t1"].run()                                           # enqueued FIRST: the host needs ~0.1 ms for the launches below
-            # small independent launches (noise draw, result-slot clear, and for data-parallel runs the global mask counts: a
-            # 4-double all-reduce) would sit on the critical chain in front of t1: on their own stream they overlap the
-            # geometry and t1; the main stream -- and through _ev[2] the actor stream -- waits for them after t1
-            sc.wait_event(self._ev[0])
-            sc.wait_event(st["ev_g"])
-            with torch.cuda.stream(sc):
-                small_inits()
-                if self.dp is not None:
-                    self.dp.set_counts(batch)
-                self._ev_counts.record(sc)
-            main.wait_event(self._ev_counts)
-            s1.wait_event(self._ev[0])
-            s1.wait_event(st["ev_g"])
-            with torch.cuda.stream(s1):
-                P["c_fwd"].run()
-        else:
-            if self.dp is not None:
-                self.dp.set_counts(batch)
-            P["c_fwd"].run()
-            small_inits()
-            P["t1"].run()
-        if OVERLAP_PASSES:
-            # The actor phase's policy forward needs nothing from the critic update: it starts as soon as t1 is done (its
-            # encoder BatchNorms must come after t1's, as in the reference) and runs beside t2 and the critic backward.
-            # On steps without the actor-critic term (update_step % policy_update_gap != 0) the WHOLE actor phase --
-            # loss, backward, Adam of policy + encoder -- is independent of the critic phase (disjoint parameters,
-            # gradient arenas, dW lanes and result slots) and runs there too.
-            self._ev[2].record(main)
-        # the rest of the target chain is enqueued BEFORE the actor pass: the host needs ~0.4 ms for the actor pass's
-        # launches, and the main stream (the critical path) would sit idle behind them
-        hip.call("gad_target_noise", self.pi_t, self.noise_u, B, float(level), int(normal_noise), self.a_next)
-        P["t2"].run()
-        if OVERLAP_PASSES:
-            s2.wait_event(self._ev[2])
-            s2.wait_event(self._ev[0])
-            s2.wait_event(st["ev_g"])
-            with torch.cuda.stream(s2):
-                P["p_fwd"].run()
-                self._policy_outputs()
-                if not policy_step:
-                    actor_tail(None)
-        if OVERLAP_PASSES:
-            self._ev[1].record(s1)
-            main.wait_event(self._ev[1])
-            # the target chain's deferred running-statistics update: on the value stream, behind the value pass's own
-            # updates (the reference's order) and the target pass (event), off the main stream's chain; the main stream picks
-            # it up again before the next writer of those statistics
-            self._ev[4].record(main)
-            s1.wait_event(self._ev[4])
-            with torch.cuda.stream(s1 if EARLY_ZERO else main):
-                if not getattr(self, "_eval", False):      # (eval-mode BatchNorm: the running statistics stay)
-                    P["t2_run"].run()
-                self._ev_run.record(s1 if EARLY_ZERO else main)
-        hip.call("gad_critic_loss", self.hs_c.out, self.hs_ct.out, d["reward_batch"], d["mask_batch"],
-                 d["perturb_flag_batch"], d["return_batch"], d["goal_batch"], B, float(ag.gamma), int(bool(ag.critic_aux)),
-                 self.inv_n_critic(), self.y, self.critic_aux_norm, self.hs_c.g_out, engine._ptr(self.scal, 0))
-        P["c_bwd"].run()
-        if OVERLAP_PASSES:
-            main.wait_event(self._ev_run)           # (long done; orders the running statistics before the next value pass)
-        if self.fused_optim:
-            self._reduce([self.cr.flat, self.venc.flat], "c")
-            if self.dp is not None:       # (single process: the backward plan's conversion launch already formed the sum of squares)
-                hip.call("gad_sumsq", self.cr.flat.grad, self.cr.flat.n, self.clip_sumsq)
-            self._optim_phase("c", policy_step)
-        else:
-            self._reduce([self.cr.flat, self.venc.flat], "c")
-            hip.call("gad_sumsq", self.cr.flat.grad, self.cr.flat.n, self.clip_sumsq)
-            self._adam(self.venc.flat, ag.state_feat_val_encoder_optim)
-            self._adam(self.cr.flat, ag.critic_optim, clip=self.clip_sumsq)
-        # ---- actor phase
-        if OVERLAP_PASSES:
-            self._ev[3].record(s2)
-            main.wait_event(self._ev[3])
-        else:
-            P["p_fwd"].run()
-            self._policy_outputs()
-        if policy_step:
-            P["v_fwd"].run()
-            hip.call("gad_actor_critic_loss", self.hs_cpi.out, d["expert_flag_batch"], d["return_batch"], B, ratio,
-                     self.inv_n_actor_critic(), self.hs_cpi.g_out, engine._ptr(self.scal, 8))
-            P["v_bwd"].run()
-            actor_tail(self.slot_v.daction)
-        elif not OVERLAP_PASSES:
-            actor_tail(None)
-        if self.fused_optim:
-            self._optim_phase("end", policy_step)
-            self._download(sync=False)
-            return
-        self._target_updates()
-        # (measured and not kept: the bookkeeping below on the small-launch lane instead of the main stream: 287 vs 297
-        # steps/s -- that lane also carries the next step's uploads and geometry)
-        self._stats()
-        if not getattr(self, "_eval", False):
-            self.enc.bump_batches_tracked(2)
-            self.venc.bump_batches_tracked(3 if policy_step else 2)
-        self._download(sync=False)
+        self._patch_and_run(ent, {}, walk)
+        self._cur_batch = None
 
     def bc_step(self, batch, sync=True):
         """one BC update.  sync=False: return a PendingStep right after the enqueue (ddpg_step's contract: up to
-        engine.HOST_RING - 1 steps ahead).  The step is one replayed launch list (_bc_replay) unless _replays() says otherwise."""
+        engine.HOST_RING - 1 steps ahead).  The step is one launch list (_build_bc_plan), replayed when _replays() says so, walked
+        from Python otherwise."""
         slot = self._begin_step(alternate=True)
-        fused = self.fused_optim and self.dp is None     # (a data-parallel BC run keeps the separate optimiser launches)
         replay = self._replays()
-        if replay:
-            self._bc_replay(batch)
-        else:
-            self._bc_enqueue(batch, fused)
-        return self._finish_step(slot, sync, replay, fused)
-
-    def _bc_enqueue(self, batch, fused):
-        """the BC step enqueued call by call on the current stream (no host synchronisation inside): what _bc_replay is
-        compared against; fused=False: the optimiser phase as separate Adam / target / statistics launches"""
-        ag, d, P = self.agent, self.dbuf, self.plans
-        B = self.B
-        st = self._sets[self._set]
-        main = torch.cuda.current_stream()
-        if st.get("prefetched") is not None:             # (staged for the replayed path, which was switched off since: dropped)
-            main.wait_stream(engine.side_stream(which=21))
-            st["prefetched"] = None
-        self.upload(batch)
-        st["ev_up"].record(main)
-        if isinstance(batch, dict) and "uploaded_event" in batch:   # (PrefetchSampler: see _stage_inputs)
-            batch["uploaded_event"] = st["ev_up"]
-        if self.dp is not None:
-            self.dp.set_counts(batch)
-        self.scal.zero_()
-        if fused:                                        # this step's Adam scalars of both networks: one upload
-            self._adam_host(self.pol.flat, ag.policy_optim)
-            if ag.train_feature:
-                self._adam_host(self.enc.flat, ag.state_feat_encoder_optim)
-            self.hyper_all.copy_(self._hyper_ring[self._slot], non_blocking=True)
-        self.geo.run(d["point_state_batch"])
-        P["p_fwd"].run()
-        self._policy_outputs()
-        hip.call("gad_actor_loss", self.hs_p.out, self.pi, d["expert_action_batch"], d["expert_flag_batch"],
-                 d["return_batch"], d["goal_batch"], B, self.pol.n_heads, 1.0, int(bool(ag.policy_aux)), self.action_scale, None,
-                 self.inv_n_actor(), self.hs_p.g_out, engine._ptr(self.scal, 4))
-        P["p_bwd"].run()
-        self._reduce([self.pol.flat, self.enc.flat], "a")      # (bucketed: the early bucket left from the plan's hook)
-        if fused:
-            self._optim_phase("a", False)                      # (carries the encoder's num_batches_tracked + 1)
-        else:
-            self._adam(self.pol.flat, ag.policy_optim)
-            if ag.train_feature:
-                self._adam(self.enc.flat, ag.state_feat_encoder_optim)
-            self._target_updates()
-            self._stats()
-            self.enc.bump_batches_tracked(1)
-        self._download(sync=False)
-
-    def _policy_outputs(self):
-        """pi = tanh(mean) * scale and the aux pose (unit quaternion + translation) when the head has one"""
-        nh = self.pol.n_heads
-        hip.call("gad_policy_outputs", self.hs_p.out, self.B, nh, self.action_scale, self.action_bias, self.pi,
-                 self.aux_pred if nh == 13 else None)
+        self._bc_run_list(batch, walk=not replay)
+        return self._finish_step(slot, sync, replay)
 
     # data-parallel hooks: device pointers to globally reduced 1/count pairs (None = local counts)
     def inv_n_critic(self):
@@ -1208,14 +1005,6 @@ class FusedRuntime(object):
 
     def _host_flags(self):
         return {k: self.dbuf[k].cpu().numpy() for k in ("return_batch", "expert_flag_batch", "perturb_flag_batch")}
-
-    def _download(self, sync=True):
-        if self.dp is not None:
-            self.dp.reduce_scalars(self.scal)
-        self.scal_host.copy_(self.scal, non_blocking=True)
-        if sync:
-            torch.cuda.current_stream().synchronize()
-        return self.scal_host.numpy()
 
 
 # ----------------------------------------------------------------------------------------------

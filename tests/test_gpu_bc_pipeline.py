@@ -1,6 +1,6 @@
 """The BC update step's host pipeline: run-ahead (update_parameters(sync=False)), prefetch into the second input / geometry set,
-the step as one replayed launch list with one fused optimiser launch -- against the synchronous loop and against the call-by-call
-enqueue it replaces as the default (runtime.STEP_PLAN = False, set_fused_optim(False), engine.SERIAL)."""
+the step as one replayed launch list with one fused optimiser launch -- against the synchronous loop and against the same list
+walked call by call from Python (runtime.STEP_PLAN = False, set_fused_optim(False), engine.SERIAL)."""
 import contextlib
 import functools
 import random

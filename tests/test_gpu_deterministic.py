@@ -2,6 +2,7 @@
 whatever the schedule -- stream interleaving, grid-rows hints, run-ahead -- and façade backward ops that do not depend on the
 order of colliding additions.  Parity with the reference in the mode goes through the helpers of tests/test_gpu_step.py."""
 import contextlib
+import functools
 
 import numpy as np
 import pytest
@@ -63,7 +64,8 @@ def _state(agent, nets, results):
     return out
 
 
-def _run_steps(cfg_name, kind, B, schedule, nsteps=6, seed=91):
+def _run_steps(cfg_name, kind, B, schedule, nsteps=6, seed=91, before_step=None):
+    """before_step(agent, i, batch): called in front of step i (switches a test flips between steps)"""
     import random
     from ga_ddpg_amd.synth_data import sample_valid_batch
     random.seed(seed)
@@ -79,6 +81,8 @@ def _run_steps(cfg_name, kind, B, schedule, nsteps=6, seed=91):
     results = []
     with _schedule(schedule):
         for i in range(nsteps):
+            if before_step is not None:
+                before_step(agent, i, batches[i])
             if kind == "bc":
                 results.append(agent.update_parameters(batches[i], agent.update_step, i))
             elif schedule == "run_ahead":
@@ -116,6 +120,108 @@ def test_det_bc_steps_bitwise_across_schedules():
         ref = _run_steps("bc_dagger_aux.yaml", "bc", 64, "default", nsteps=4)
         for sched in ("serial", "no_row_hints"):
             _assert_bitwise(ref, _run_steps("bc_dagger_aux.yaml", "bc", 64, sched, nsteps=4), sched)
+
+
+# ------------------------------------------------------------------------------------------------ one list, two ways to run it
+@contextlib.contextmanager
+def _path(name):
+    """no_step_plan: the step's launch list walked item by item from Python (runtime.STEP_PLAN off); plan_py: every plan walked
+    (engine.USE_C_PLANS off); unfused is a property of the runtime (_unfused_from_step_0)"""
+    from ga_ddpg_amd import engine, runtime
+    saved = (runtime.STEP_PLAN, engine.USE_C_PLANS)
+    runtime.STEP_PLAN = name != "no_step_plan"
+    engine.USE_C_PLANS = name != "plan_py"
+    try:
+        yield
+    finally:
+        runtime.STEP_PLAN, engine.USE_C_PLANS = saved
+
+
+def _unfused_from_step_0(agent, i, batch):
+    if i == 0:
+        ps = batch["point_state_batch"]
+        agent.runtime(ps.shape[0], ps.shape[2]).set_fused_optim(False)
+
+
+PATH_B, PATH_STEPS = 32, 4
+
+
+@functools.lru_cache(maxsize=None)
+def _ddpg_path_run(path):
+    """four DDPG steps at B = 32 from update_step = 1 with injected noise -> (_state, [was step i a policy step]).  Call inside _mode()."""
+    kinds = []
+
+    def before(agent, i, batch):
+        kinds.append(agent.update_step % agent.policy_update_gap == 0)
+        if path == "unfused":
+            _unfused_from_step_0(agent, i, batch)
+    with _path(path):
+        state = _run_steps("ddpg_td3_aux.yaml", "ddpg", PATH_B, "default", nsteps=PATH_STEPS, before_step=before)
+    return state, tuple(kinds)
+
+
+@pytest.mark.parametrize("path", ["no_step_plan", "unfused", "plan_py"])
+def test_det_ddpg_paths_bitwise(path):
+    """the replayed list with the fused optimiser launches (default) against: the same list walked from Python; the separate
+    gad_sumsq / Adam / target / statistics launches; every plan walked instead of replayed in C -- two policy and two non-policy
+    steps, every tensor the steps wrote and the logs agree bit for bit"""
+    with _mode():
+        ref, kinds = _ddpg_path_run("default")
+        assert len(ref) > 100 and sorted(kinds) == [False, False, True, True]
+        got, kinds_got = _ddpg_path_run(path)
+        assert kinds_got == kinds
+        _assert_bitwise(ref, got, path)
+
+
+def test_det_steps_alternate_walk_and_replay():
+    """replayed, walked, replayed, walked steps on ONE runtime (runtime.STEP_PLAN flipped between steps) equal four replayed steps
+    bit for bit: what the two ways share -- the patched items' cache of last values, the input sets' `prefetched` marks -- survives
+    the change of mode"""
+    from ga_ddpg_amd import runtime
+    seen = []
+
+    def flip(agent, i, batch):
+        runtime.STEP_PLAN = i % 2 == 0
+        if agent._rt is not None:
+            seen.append(agent._rt._replays())
+    with _mode():
+        for cfg_name, kind in (("ddpg_td3_aux.yaml", "ddpg"), ("bc_dagger_aux.yaml", "bc")):
+            ref = _ddpg_path_run("default")[0] if kind == "ddpg" else _run_steps(cfg_name, kind, PATH_B, "default", nsteps=PATH_STEPS)
+            del seen[:]
+            with _path("default"):                  # (restores STEP_PLAN)
+                got = _run_steps(cfg_name, kind, PATH_B, "default", nsteps=PATH_STEPS, before_step=flip)
+            assert seen == [False, True, False]
+            _assert_bitwise(ref, got, kind + ": alternating walked and replayed steps")
+
+
+def test_det_ddpg_eval_mode_step_with_unfused_optimiser():
+    """update_parameters(test=True) after set_fused_optim(False), a non-policy and a policy step at B = 32: num_batches_tracked of
+    both encoders and every running statistic stay, and the log equals the fused eval-mode step's"""
+    from oracle.detfill import fill_running_stats_
+    from ga_ddpg_amd.synth_data import sample_valid_batch
+    rng = np.random.default_rng(78)
+    batch = sample_valid_batch(_memory("ddpg_td3_aux.yaml", 6), PATH_B, rng)
+    noise = rng.random((PATH_B, 6)).astype(np.float32)
+    with _mode():
+        for start in (1, 2):
+            logs = {}
+            for fused in (True, False):
+                agent, nets = tstep._filled_agent("ddpg_td3_aux.yaml", 91)
+                for name, net in nets.items():
+                    fill_running_stats_(net, name, 91)
+                agent.update_step = start
+                agent.runtime(PATH_B, batch["point_state_batch"].shape[2]).set_fused_optim(fused)
+                before = {k: v.detach().cpu().clone() for k, v in agent.state_feature_extractor.state_dict().items()
+                          if "running" in k or "num_batches" in k}
+                assert sum("num_batches" in k for k in before) >= 2 and any("value_encoder" in k for k in before) and len(before) >= 60
+                logs[fused] = {k: float(v) for k, v in agent.update_parameters(batch, agent.update_step, 0, test=True, noise_u=noise).items()}
+                torch.cuda.synchronize()
+                after = agent.state_feature_extractor.state_dict()
+                for k, v in before.items():
+                    assert torch.equal(after[k].cpu(), v), "eval-mode step (fused=%s) touched %s" % (fused, k)
+            assert logs[True].keys() == logs[False].keys() and len(logs[True]) == 11
+            for k in logs[True]:
+                assert np.float64(logs[True][k]).tobytes() == np.float64(logs[False][k]).tobytes(), (start, k, logs[True][k], logs[False][k])
 
 
 def _routed_families(nsteps=1):

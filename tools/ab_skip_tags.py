@@ -2,9 +2,12 @@
 tag starts with one of the given prefixes SKIPPED (stale buffers are read instead: the numbers of such a step are garbage,
 its schedule and every other launch are unchanged).  Answers "how much faster would the step be if this family cost
 nothing?" -- the upper bound of any optimisation of that family, which its stand-alone duration does not tell (a launch
-on a side lane that fills the chain's gaps is nearly free; one on the dX chain costs its full duration).
+on a side lane that fills the chain's gaps is nearly free; one on the dX chain costs its full duration).  The launches are
+taken out of the replayed step and prefetch lists themselves, so what is measured is the default schedule.  Further tokens:
+"optim" = the gad_optim_jobs launches, "geometry" = both cloud sets' geometry, "plan:NAME" = every launch of
+FusedRuntime.plans[NAME].
 
-    python tools/ab_skip_tags.py "dw." "dx.sa2,dx.sa3" "fwd.sa1.l1" "name:gad_bn_finalize" "untagged:gad_gemm_fwd" ...
+    python tools/ab_skip_tags.py "dw." "dx.sa2,dx.sa3" "fwd.sa1.l1" "name:gad_bn_finalize" "untagged:gad_gemm_fwd" "optim" "plan:p_fwd" ...
 """
 import os
 import sys
@@ -43,47 +46,46 @@ def main():
     skip = {"prefixes": ()}
     plain_run = engine.Plan.run
 
-    def run(self):
+    def items_of(plans):
+        """ids of the plans' items and of every copy Plan.extend made of them (the step list holds the copies)"""
+        ids, todo = set(), [it for p in plans if p is not None for it in p.calls]
+        while todo:
+            it = todo.pop()
+            ids.add(id(it))
+            todo += it.clones
+        return ids
+
+    def run(self, walk=False):
+        """the step list / prefetch list (and any other plan) minus the skipped launches, replayed like any plan"""
         pre = skip["prefixes"]
         if not pre:
-            return plain_run(self)
-        plans = tuple(x.split(":", 1)[1] for x in pre if x.startswith("plan:"))            # whole plans of the runtime ("plan:p_fwd")
-        if plans:
-            rt = agent._rt
-            for st in rt._sets:
-                if any(st["plans"].get(k) is self for k in plans):
-                    return
-        tagp = tuple(x for x in pre if ":" not in x and x not in ("optim", "geometry"))
-        names = tuple(x.split(":", 1)[1] for x in pre if x.startswith("name:"))            # every call of that entry point
-        untag = tuple(x.split(":", 1)[1] for x in pre if x.startswith("untagged:"))        # its untagged calls (the heads' GEMMs)
+            return plain_run(self, walk)
         key = (id(self), pre)
         filt = filtered.get(key)
         if filt is None or filt.n_src != len(self.calls):
-            filt = engine.Plan()                    # the same items minus the skipped launches (compiled and replayed like any plan)
+            sets = agent._rt._sets
+            whole = []                                                                     # plans skipped as a whole:
+            for x in pre:
+                if x.startswith("plan:"):                                                  # "plan:p_fwd": that plan of every input set
+                    whole += [st["plans"].get(x.split(":", 1)[1]) for st in sets]
+                elif x == "geometry":                                                      # FPS / ball query / row compaction of both cloud sets
+                    whole += [st.get(k) for st in sets for k in ("geo_plan", "geo_next_plan")]
+            gone = items_of(whole)
+            tagp = tuple(x for x in pre if ":" not in x and x not in ("optim", "geometry"))
+            names = tuple(x.split(":", 1)[1] for x in pre if x.startswith("name:"))        # every call of that entry point
+            if "optim" in pre:                                                             # the fused optimiser launches
+                names += ("gad_optim_jobs",)
+            untag = tuple(x.split(":", 1)[1] for x in pre if x.startswith("untagged:"))    # its untagged calls (the heads' GEMMs)
+            filt = engine.Plan()
             filt.calls = [it for it in self.calls if not (it.kind == "call" and (
-                (tagp and it.tag is not None and it.tag.startswith(tagp)) or it.name in names or (it.name in untag and it.tag is None)))]
+                id(it) in gone or (tagp and it.tag is not None and it.tag.startswith(tagp)) or it.name in names or
+                (it.name in untag and it.tag is None)))]
             filt.keep = [self]
             filt.n_src = len(self.calls)
             filtered[key] = filt
-        return plain_run(filt)
+        return plain_run(filt, walk)
     filtered = {}
     engine.Plan.run = run
-    from ga_ddpg_amd import runtime as rtm
-    rtm.STEP_PLAN = False       # the step enqueued phase by phase (each plan still replayed in C): whole phases can be skipped from here
-    plain_optim = rtm.FusedRuntime._optim_phase
-
-    def optim(self, which, policy_step):                       # token "optim": the fused optimiser launches (gad_optim_jobs)
-        if "optim" in skip["prefixes"]:
-            return
-        return plain_optim(self, which, policy_step)
-    rtm.FusedRuntime._optim_phase = optim
-    plain_geo = engine.Geometry.run
-
-    def geo_run(self, pts):                                    # token "geometry": FPS / ball query / row compaction of both cloud sets
-        if "geometry" in skip["prefixes"]:
-            return
-        return plain_geo(self, pts)
-    engine.Geometry.run = geo_run
 
     def rate(n=150):
         for i in range(20):

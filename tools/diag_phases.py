@@ -57,7 +57,7 @@ def main():
             wrap(p, "run", k)
     wrap(rt.geo, "run", "geo(cur)")
     wrap(rt.geo_next, "run", "geo(next)")
-    for a in ("_adam", "_stats", "_target_updates", "_download", "upload", "_reduce"):
+    for a in ("_adam", "_stats", "_target_updates", "upload", "_reduce"):
         wrap(rt, a, a)
     if rt.dp is not None:
         wrap(rt.dp, "set_counts", "dp.set_counts")
