@@ -8,6 +8,13 @@ only owns device memory and the stream.  A *plan* is a list of pre-built calls o
 Reference structure mirrored: core/networks.py:65-92 (base_network = SA1, SA2, SA3, FC head),
 :253-300 (QNetwork), :303-371 (GaussianPolicy); upstream PointnetSAModule.forward.
 """
+import copy
+import ctypes as C
+import os
+import struct
+import sys
+import weakref
+
 import numpy as np
 import torch
 
@@ -377,7 +384,6 @@ class EncoderSlot(object):
 def slot_view(slot, geo):
     """the same activation buffers bound to another Geometry of the same shape (the runtime alternates between two input /
     geometry sets; the multi-GB activation scratch exists once)"""
-    import copy
     assert [r["cap"] for r in geo.rows] == [r["cap"] for r in slot.geo.rows] and geo.B == slot.B
     v = copy.copy(slot)
     v.geo = geo
@@ -506,35 +512,7 @@ def serial():
 #   next step's uploads + geometry (20, 21) ride on A: behind the critic backward's weight gradients of the step before, they
 #   start while that step's tail (actor phase / optimiser) still runs; on C they sat behind the actor backward's weight
 #   gradients, i.e. until the very end of the step (round 3, same box: 316 -> 320 steps/s; on B: no change)
-import os as _os
 _PHYS = {1: "A", 11: "A", 2: "B", 12: "C", 3: "C", 20: "A", 21: "A"}
-if _os.environ.get("GAD_STREAM_MAP"):                     # e.g. "1:A,11:A,2:B,12:C,3:C,20:D,21:D"
-    _PHYS = dict((int(kv.split(":")[0]), kv.split(":")[1]) for kv in _os.environ["GAD_STREAM_MAP"].split(","))
-
-
-def _masked_stream(dev, letter):
-    """A/B switch GAD_CU_MASK_<letter> = "<n>" (the n lowest CU bits) or "even" / "odd" (every second CU) / hex words "w0,w1,...":
-    the physical side stream `letter` is created with hipExtStreamCreateWithCUMask -- its kernels (e.g. the weight-gradient lanes)
-    may then only occupy those CUs and leave the others to the chains (profiles/README.md round 5: measured, not kept)."""
-    spec = _os.environ.get("GAD_CU_MASK_" + letter)
-    if not spec:
-        return None
-    import ctypes as C
-    if spec in ("even", "odd"):
-        words = [0x55555555 if spec == "even" else 0xAAAAAAAA] * 8
-    elif "," in spec or spec.startswith("0x"):
-        words = [int(w, 16) for w in spec.split(",")]
-    else:
-        n = int(spec)
-        words = [(0xFFFFFFFF if n >= 32 * (i + 1) else ((1 << max(0, n - 32 * i)) - 1)) & 0xFFFFFFFF for i in range(8)]
-    rt = C.CDLL("libamdhip64.so")
-    st = C.c_void_p()
-    arr = (C.c_uint32 * len(words))(*words)
-    with torch.cuda.device(dev):
-        rc = rt.hipExtStreamCreateWithCUMask(C.byref(st), C.c_uint32(len(words)), arr)
-    if rc != 0:
-        raise RuntimeError("hipExtStreamCreateWithCUMask failed (%d)" % rc)
-    return torch.cuda.ExternalStream(st.value, device=dev)
 
 
 def side_stream(device=None, which=0):
@@ -548,52 +526,27 @@ def side_stream(device=None, which=0):
     if key not in _SIDE:
         for k in ("A", "B", "C"):                # fixed creation order: the first three side streams get queues of their own
             if (dev, k) not in _SIDE:
-                _SIDE[(dev, k)] = _masked_stream(dev, k) or torch.cuda.Stream(device=dev)
+                _SIDE[(dev, k)] = torch.cuda.Stream(device=dev)
         if key not in _SIDE:
             _SIDE[key] = torch.cuda.Stream(device=dev)
     return _SIDE[key]
 
 
-# Wavefront issue priority per lane (include/gaddpg.h: gad_stream_priority): "main:3,B:1" raises the GEMM-family launches of the
-# caller's stream (the TD-target / critic chain the step waits for) and of the actor lane above the weight-gradient lanes'
-# wavefronts they share SIMDs with.  s_setprio inside the kernels: no stream priority, the four-queue mapping is untouched.
-LANE_PRIO = _os.environ.get("GAD_LANE_PRIO", "")
-_PRIO_DONE = set()
-
-
-def apply_lane_priorities(main):
-    """once per caller's stream: hand the GAD_LANE_PRIO table to the library"""
-    if not LANE_PRIO or serial():
-        return
-    dev = main.device.index
-    key = (dev, int(main.cuda_stream))
-    if key in _PRIO_DONE:
-        return
-    _PRIO_DONE.add(key)
-    from . import hip
-    for kv in LANE_PRIO.split(","):
-        name, pr = kv.split(":")
-        st = main if name == "main" else side_stream(dev, {"A": 1, "B": 2, "C": 3}[name])
-        hip.check(hip.lib().gad_stream_priority(hip.C.c_void_p(int(st.cuda_stream)), int(pr)), "gad_stream_priority")
-
-
-CONCURRENT_DW = _os.environ.get("GAD_CONCURRENT_DW", "1") == "1"      # fork dW GEMMs onto side streams (they feed nothing but the optimiser)
-FUSED_SA1_BWD = _os.environ.get("GAD_FUSED_SA1_BWD", "1") == "1"     # SA1 l3 / l2 backward: dX + dW in one kernel (gad_gemm_bwd)
-RECOMP_SA1 = _os.environ.get("GAD_RECOMP_SA1", "0") == "1"   # SA1 layer 2 recomputes layer 1's output from the gathered rows (gad_gemm_fwd mode 2); layer 1 stores nothing in a pass that is never
+CONCURRENT_DW = os.environ.get("GAD_CONCURRENT_DW", "1") == "1"      # fork dW GEMMs onto side streams (they feed nothing but the optimiser)
+FUSED_SA1_BWD = os.environ.get("GAD_FUSED_SA1_BWD", "1") == "1"     # SA1 l3 / l2 backward: dX + dW in one kernel (gad_gemm_bwd)
+RECOMP_SA1 = os.environ.get("GAD_RECOMP_SA1", "0") == "1"   # SA1 layer 2 recomputes layer 1's output from the gathered rows (gad_gemm_fwd mode 2); layer 1 stores nothing in a pass that is never
                                                              # back-propagated.  OFF: bit-equal, measured neutral (layer 2 +1.9 us, layer 1 -2.6 us: the re-gather costs what z1's read cost)
-INLINE_BN_BWD = _os.environ.get("GAD_INLINE_BN_BWD", "1") == "1"     # BatchNorm-backward coefficients formed in the dX / dW prologues
-DEFER_BN_STAGES = tuple(int(c) for c in _os.environ.get("GAD_DEFER_BN_STAGES", "012"))     # SA stages it applies to (A/B)
-DEFER_BN_WIDE = _os.environ.get("GAD_DEFER_BN_WIDE", "1") == "1"     # SA2 / SA3 layers 1, 2: BatchNorm finalised in the consumer GEMM's prologue
-DEFER_DW = _os.environ.get("GAD_DEFER_DW", "0") == "1"              # A/B: weight-gradient GEMMs of a pass launched after its dX chain
-FUSED_WIDE_BWD = _os.environ.get("GAD_FUSED_WIDE_BWD", "0") == "1"   # SA2 / SA3 backward: dX + dW in one kernel (round 4; the reduce of its
+INLINE_BN_BWD = os.environ.get("GAD_INLINE_BN_BWD", "1") == "1"     # BatchNorm-backward coefficients formed in the dX / dW prologues
+DEFER_BN_STAGES = tuple(int(c) for c in os.environ.get("GAD_DEFER_BN_STAGES", "012"))     # SA stages it applies to (A/B)
+DEFER_BN_WIDE = os.environ.get("GAD_DEFER_BN_WIDE", "1") == "1"     # SA2 / SA3 layers 1, 2: BatchNorm finalised in the consumer GEMM's prologue
+FUSED_WIDE_BWD = os.environ.get("GAD_FUSED_WIDE_BWD", "0") == "1"   # SA2 / SA3 backward: dX + dW in one kernel (round 4; the reduce of its
                                                                      # partial dW blocks forked onto the weight-gradient lane).  OFF: measured 4 - 6 % slower at B = 256 and 512 --
                                                                      # the step follows the length of its dX chain, and dW on its own lane is nearly free (DESIGN.md 5.4)
 WIDE_SLAB_ELEMS = 9 * 1024 * 1024        # floats per fused wide layer's partial-dW workspace (library option bwd_wide_slab <= 8)
 DW_REDUCE_LATER = -2                     # include/gaddpg.h GAD_DW_REDUCE_LATER
-DW_LANES = 1              # number of dW side streams (2 measured no faster: the overlapped kernels already saturate the GPU) the layers alternate between (each with its own partial workspace)
 
 
-USE_C_PLANS = _os.environ.get("GAD_PLAN_C", "1") == "1"     # replay plans through gad_plan_run (one foreign call per plan segment);
+USE_C_PLANS = os.environ.get("GAD_PLAN_C", "1") == "1"     # replay plans through gad_plan_run (one foreign call per plan segment);
                                                             # 0: the item-by-item Python walk (the same launches in the same order)
 _ROUTES = hip.ROUTES       # tag -> kernel family (gad_last_kernel), learnt by the Python walk; cleared when a library option changes
 
@@ -601,13 +554,17 @@ _ROUTES = hip.ROUTES       # tag -> kernel family (gad_last_kernel), learnt by t
 class _Item(object):
     """one entry of a Plan: kind in {"call", "wait", "record", "wait_event", "zero", "memcpy", "py"}; `on` = the logical stream
     (0 = the stream that is current when the plan runs, else a side_stream `which`)"""
-    __slots__ = ("kind", "on", "name", "f", "argv", "words", "kinds", "on2", "event", "holder", "tensor", "tag", "cpos", "clones")
+    __slots__ = ("kind", "on", "name", "f", "argv", "words", "kinds", "on2", "event", "holder", "tensor", "tag", "cpos", "clones",
+                 "__weakref__")
 
     def __init__(self, kind, on=0):
         self.kind, self.on = kind, on
         self.name = self.f = self.argv = self.words = self.kinds = self.on2 = self.event = self.holder = self.tensor = self.tag = None
-        self.cpos = []         # [(compiled plan, item index)]: where this item sits in gad_plans (an item may be shared by plans)
-        self.clones = []       # copies made by Plan.extend(on=...): a patch of this item reaches them too
+        # Where this item sits in gad_plans: [(weak reference to the _Compiled, segment, item index)].  An item may be shared by plans
+        # and outlives most of them; the handles are the _Compiled's, so a position dies with it (_Compiled.__init__ and
+        # Plan.patch drop the dead ones they meet)
+        self.cpos = []
+        self.clones = weakref.WeakSet()       # copies made by Plan.extend(on=...), while their plans live: a patch of this item reaches them too
 
 
 class EventHolder(object):
@@ -623,8 +580,6 @@ class EventHolder(object):
 
 def _pack_words(argv):
     """ctypes arguments -> (uint64 words, GAD_ARG_* kinds) of a gad_plan_add_call item"""
-    import ctypes as C
-    import struct
     words, kinds = [], []
     for x in argv:
         if isinstance(x, C.c_void_p):
@@ -645,7 +600,6 @@ def _pack_words(argv):
 
 
 def _float_word(v):
-    import struct
     return struct.unpack("<I", struct.pack("<f", float(v)))[0]
 
 
@@ -653,9 +607,9 @@ class _Compiled(object):
     """a Plan lowered to gad_plans: the segments between host callbacks, each replayed by one gad_plan_run"""
 
     def __init__(self, plan):
-        import ctypes as C
         L = hip.lib()
-        self.handles = []          # one gad_plan per segment
+        me = weakref.ref(self)
+        self.handles = []          # one gad_plan per segment; destroyed with this object, which is all that reaches them
         self.steps = []            # [("c", handle index) | ("py", item)]
         self.whichs = [0]          # dense lane -> logical stream
         self.timed = []            # [(segment handle index, item index in it, tag)] of the tagged launches
@@ -701,13 +655,12 @@ class _Compiled(object):
                 raise RuntimeError("unknown plan item %r" % it.kind)
             if rc < 0:
                 raise RuntimeError("plan item %s failed to compile (status %d): %s" % (it.name or it.kind, rc, L.gad_last_error().decode()))
-            it.cpos.append((cur, rc))
+            it.cpos = [p for p in it.cpos if p[0]() is not None] + [(me, len(self.handles) - 1, rc)]
         self.n_items = len(plan.calls)
         self._tables = {}
 
     def table(self, main_handle):
         """lane -> hipStream_t table for a run whose current stream is main_handle"""
-        import ctypes as C
         key = (int(main_handle or 0), serial())
         t = self._tables.get(key)
         if t is None:
@@ -716,12 +669,12 @@ class _Compiled(object):
         return t
 
     def __del__(self):
-        import sys
         if sys is None or sys.is_finalizing():      # interpreter exit: the HIP runtime may be gone already, the process frees everything
             return
         try:
             L = hip.lib()
-            for h in self.handles:
+            hs, self.handles = self.handles, ()     # (a weak reference may still resolve inside __del__: Plan.patch finds no handle)
+            for h in hs:
                 L.gad_plan_destroy(h)
         except Exception:
             pass
@@ -752,7 +705,6 @@ class Plan(object):
 
     def call(self, name, *a, side=False, on=None):
         """-> the item (for patch()); arguments as hip.call takes them, plus ctypes structures / arrays (passed by address)"""
-        import ctypes as C
         it = _Item("call", (10 + int(side)) if side else (on or 0))
         it.name, it.f = name, getattr(hip.lib(), name)
         it.argv = hip._args(*a)
@@ -769,7 +721,6 @@ class Plan(object):
 
     def zero_multi(self, tensors, on=0):
         """clear several buffers with ONE launch per six of them (gad_zero_buffers) instead of a fill kernel each"""
-        import ctypes as C
         ts = [t for t in tensors if t is not None]
         for i in range(0, len(ts), 6):
             grp = ts[i:i + 6]
@@ -819,12 +770,11 @@ class Plan(object):
 
     def extend(self, other, on=0):
         """append another plan's items; on != 0: the other plan's main stream becomes logical stream `on` here"""
-        import copy
         for it in other.calls:
             if on and (it.on == 0 or (it.kind == "wait" and it.on2 == 0)):
                 src, it = it, copy.copy(it)
-                src.clones.append(it)
-                it.cpos, it.clones = [], []
+                src.clones.add(it)               # (weakly: the copy goes with this plan)
+                it.cpos, it.clones = [], weakref.WeakSet()
                 if it.kind == "wait":
                     it.event = torch.cuda.Event()
                     it.on2 = on if it.on2 == 0 else it.on2
@@ -839,7 +789,6 @@ class Plan(object):
     def patch(it, index, value):
         """replace argument `index` of a call item (a Python float / int / hip.Ptr / tensor / None, converted like hip.call
         does), or word `index` of a memcpy item (an address), or the event of a record / wait_event item (EventHolder | None)"""
-        import ctypes as C
         if it.kind == "call":
             new = hip._args(value)[0]
             it.argv[index] = new
@@ -854,13 +803,16 @@ class Plan(object):
             it.holder = value
             word = value.handle if value is not None else 0
         L = hip.lib()
-        for h, i in it.cpos:
-            hip.check(L.gad_plan_patch(h, i, index, C.c_uint64(word)), "gad_plan_patch")
-        for cl in it.clones:           # (argv / words lists are shared with the clones; their compiled words and holders are not)
-            if cl.kind not in ("call", "memcpy"):
-                cl.holder = it.holder
-            for h, i in cl.cpos:
-                hip.check(L.gad_plan_patch(h, i, index, C.c_uint64(word)), "gad_plan_patch")
+        for x in (it, *it.clones):     # (argv / words lists are shared with the clones; their compiled words and holders are not)
+            if x.kind not in ("call", "memcpy"):
+                x.holder = it.holder
+            live = []
+            for p in x.cpos:
+                c = p[0]()
+                if c is not None and c.handles:          # else: that compiled plan is gone, and its handles with it
+                    hip.check(L.gad_plan_patch(c.handles[p[1]], p[2], index, C.c_uint64(word)), "gad_plan_patch")
+                    live.append(p)
+            x.cpos = live
 
     # ---- replay -------------------------------------------------------------------------------------------------------
     def run(self, walk=False):
@@ -870,22 +822,20 @@ class Plan(object):
         if walk or not USE_C_PLANS or (timed and any(it.tag is not None and it.name in _TIMED_CALLS and it.tag not in _ROUTES
                                               for it in self.calls)):
             return self.run_py()
-        import ctypes as C
+        if self._c is not None and self._c.n_items != len(self.calls):
+            self._c = None                 # (released before its successor is built: its positions leave the items with it)
         c = self._c
-        if c is None or c.n_items != len(self.calls):
+        if c is None:
             c = self._c = _Compiled(self)
         L = hip.lib()
         main = torch.cuda.current_stream()
         table = c.table(main.cuda_stream)
         if timed:
             for hi, idx, tag in c.timed:
-                if TIMING["next"] < TIMING["slots"].shape[0] and _timing_wants(tag):
-                    k = TIMING["next"]
-                    TIMING["next"] = k + 1
-                    TIMING["tags"].append(tag)
+                slot = _timing_slot(tag)
+                if slot is not None:
                     TIMING["routed"][tag] = _ROUTES[tag]
-                    hip.check(L.gad_plan_arm_timing(c.handles[hi], idx, C.c_void_p(TIMING["slots"].data_ptr() + 16 * TIMING_WAVES * k)),
-                              "gad_plan_arm_timing")
+                    hip.check(L.gad_plan_arm_timing(c.handles[hi], idx, slot), "gad_plan_arm_timing")
         n = len(table)
         for kind, x in c.steps:
             if kind == "c":
@@ -900,7 +850,6 @@ class Plan(object):
 
     def run_py(self):
         """the same launches, item by item from Python (diagnostics; also learns the kernel family of every tagged launch)"""
-        import ctypes as C
         main = torch.cuda.current_stream()
         st = hip.stream()
         sides = {}            # logical stream -> (torch stream, raw handle)
@@ -924,19 +873,15 @@ class Plan(object):
                 continue
             so, q = stream_of(it.on)
             if kind == "call":
-                took_slot = False
-                if timed and it.name in _TIMED_CALLS and it.tag is not None and TIMING["next"] < TIMING["slots"].shape[0] and \
-                        _timing_wants(it.tag):
-                    k = TIMING["next"]
-                    TIMING["next"] = k + 1
-                    TIMING["tags"].append(it.tag)
-                    hip.lib().gad_timing_slot(C.c_void_p(TIMING["slots"].data_ptr() + 16 * TIMING_WAVES * k))   # consumed by the call below
-                    took_slot = True
+                tagged = it.tag is not None and it.name in _TIMED_CALLS
+                slot = _timing_slot(it.tag) if timed and tagged else None
+                if slot is not None:
+                    hip.lib().gad_timing_slot(slot)                             # consumed by the call below
                 argv = [C.byref(x) if isinstance(x, (C.Structure, C.Array)) else x for x in it.argv]
                 hip.check(it.f(*(argv + [q])), it.name)
-                if it.tag is not None and it.name in _TIMED_CALLS:
+                if tagged:
                     _ROUTES[it.tag] = hip.lib().gad_last_kernel().decode()      # kernel family the call routed to
-                    if took_slot:
+                    if slot is not None:
                         TIMING["routed"][it.tag] = _ROUTES[it.tag]
             elif kind == "zero":
                 with torch.cuda.stream(so):
@@ -965,7 +910,6 @@ _HIPRT = []
 
 def _hip_runtime():
     if not _HIPRT:
-        import ctypes as C
         _HIPRT.append(C.CDLL("libamdhip64.so"))
     return _HIPRT[0]
 
@@ -973,6 +917,17 @@ def _hip_runtime():
 def _timing_wants(tag):
     t = TIMING["tag"]
     return t == "*" or tag == t or (isinstance(t, (set, frozenset, tuple, list)) and tag in t)
+
+
+def _timing_slot(tag):
+    """claim the next timing slot for a launch tagged `tag` -> its address (for gad_plan_arm_timing / gad_timing_slot), or None
+    when the probe does not want the tag or every slot is taken"""
+    k = TIMING["next"]
+    if k >= TIMING["slots"].shape[0] or not _timing_wants(tag):
+        return None
+    TIMING["next"] = k + 1
+    TIMING["tags"].append(tag)
+    return C.c_void_p(TIMING["slots"].data_ptr() + 16 * TIMING_WAVES * k)
 
 
 def timing_routes():
@@ -1255,7 +1210,6 @@ def plan_encoder_backward(enc, slot, g_fc2, action=None, want_dw=True, want_dact
 
     dw_lanes = []
     fused_dw = []
-    deferred_dw = []
     has_dx_now = [True]                # (set by layer(): a layer without a dX launch cannot take the fused call)
 
     def dw(s, l, dz, m, action):
@@ -1279,18 +1233,14 @@ def plan_encoder_backward(enc, slot, g_fc2, action=None, want_dw=True, want_dact
             a.row_splits = DW_REDUCE_LATER
             fused_dw.append(a)
             return
-        lane = dw_lane + (len(dw_lanes) % DW_LANES) if CONCURRENT_DW else 0
+        lane = dw_lane if CONCURRENT_DW else 0         # one weight-gradient lane per pass (two measured no faster: the overlapped kernels already saturate the GPU)
         dw_lanes.append(lane)
         ws = dw_workspace(enc.flat.device, lane=lane)
         a.partial, a.partial_elems = _ptr(ws), ws.numel()
-        tag = "dw.%s.l%d" % ("sa%d" % (s + 1) if s < 3 else "fc", l + 1)
-        if DEFER_DW and lane:                 # A/B: every weight-gradient GEMM of the pass behind its dX chain (one fork at the end)
-            deferred_dw.append((a, lane, tag))
-            return
         if lane:
             plan.fork(lane)
         plan.call_struct("gad_gemm_dw", a, side=lane)
-        plan.tag_last(tag)
+        plan.tag_last("dw.%s.l%d" % ("sa%d" % (s + 1) if s < 3 else "fc", l + 1))
 
     def layer(s, l, m, z, count, has_dx, **src):
         """(dz for the dW, dz for the dX) of one layer: the dX carries the arena accumulation of dgamma / dbeta when
@@ -1350,11 +1300,6 @@ def plan_encoder_backward(enc, slot, g_fc2, action=None, want_dw=True, want_dact
                 plan.zero(slot.daction)
             dx(dict(rows_kw, layer=1), d, m1, m1.k_in, epilogue=1, dfeat=None, feat_c=4, row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]),
                daction=_ptr(slot.daction), act_c=6, grp_per_sample=geo.M1)
-    for lane in sorted(set(l for _, l, _ in deferred_dw)):
-        plan.fork(lane)
-    for a, lane, tag in deferred_dw:
-        plan.call_struct("gad_gemm_dw", a, side=lane)
-        plan.tag_last(tag)
     for lane in sorted(set(dw_lanes) - {0}):
         plan.join(lane)
     return plan

@@ -935,7 +935,6 @@ class FusedRuntime(object):
     def _take_inputs(self, batch, st, ent, walk):
         """the step's inputs: staged now, unless prefetch_inputs() staged this very batch object into the set already (a walked
         step always stages its own, in front of its launches: prefetch_inputs() defers nothing to it)"""
-        engine.apply_lane_priorities(torch.cuda.current_stream())
         staged, st["prefetched"] = st.get("prefetched"), None
         if walk or staged is None or staged is not batch:
             self._stage_inputs(batch, st, ent["pre"], walk)

@@ -194,6 +194,34 @@ def test_det_steps_alternate_walk_and_replay():
             _assert_bitwise(ref, got, kind + ": alternating walked and replayed steps")
 
 
+def test_det_steps_across_discarded_step_lists():
+    """three steps, the step lists thrown away twice (agent.clip_grad, part of _step_key(), set to another value -- a list is built
+    under it and never run -- and back), three more steps: the per-pass plans and their items outlive the compiled lists that
+    were destroyed, and Plan.patch goes on writing through those items.  Replayed in C, this equals the same sequence walked from
+    Python (engine.USE_C_PLANS off: no compiled handles at all) bit for bit"""
+    cleared = []
+
+    def before(agent, i, batch):
+        if i != 3:
+            return
+        rt, keep = agent._rt, agent.clip_grad
+        old = rt._step_plans["key"]
+        agent.clip_grad = 2.0 * keep
+        rt._step_plan(rt._set, False)
+        cleared.append(rt._step_plans["key"] != old)
+        agent.clip_grad = keep
+        cleared.append(rt._step_key() == old)          # (step 3 finds another key than the cache's: cleared a second time)
+    with _mode():
+        runs = {}
+        for path in ("default", "plan_py"):
+            del cleared[:]
+            with _path(path):
+                runs[path] = _run_steps("ddpg_td3_aux.yaml", "ddpg", PATH_B, "default", nsteps=6, before_step=before)
+            assert cleared == [True, True]
+        assert len(runs["default"]) > 100
+        _assert_bitwise(runs["default"], runs["plan_py"], "step lists discarded between steps: replayed vs walked")
+
+
 def test_det_ddpg_eval_mode_step_with_unfused_optimiser():
     """update_parameters(test=True) after set_fused_optim(False), a non-policy and a policy step at B = 32: num_batches_tracked of
     both encoders and every running statistic stay, and the log equals the fused eval-mode step's"""
