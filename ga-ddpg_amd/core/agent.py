@@ -102,8 +102,12 @@ class Agent(object):
         """Stage the NEXT update's minibatch while the current one runs (its upload and the furthest-point-sampling / ball-query
         geometry of both cloud sets -- of the one a BC agent has -- on the prefetch lanes): the following
         update_parameters(batch_data) -- the same object -- starts from there.  A hint: results never depend on it;
-        device-resident minibatches only.  -> True if the hint will be used, False otherwise (host batches, no runtime yet,
-        a step whose launch list is walked from Python instead of replayed, such as a data-parallel BC run)."""
+        device-resident minibatches only.  -> True if the hint was TAKEN, False otherwise (host batches, no runtime yet, a
+        runtime whose launch list is walked from Python instead of replayed, such as a data-parallel BC run, the one-stream
+        schedule of the deterministic mode).  Taken is not used: the minibatch is staged behind the update that follows this
+        call, when that update is replayed -- a walked one (update_parameters(test=True)) drops the hint -- and the update after
+        it starts from there only if it gets this very object; given any other minibatch it stages its own.  A lazy handle that
+        was hinted and never passed to an update should go back through DeviceReplay.release()."""
         if self._rt is None or batch_data is None:
             return False
         return bool(self._rt.prefetch_inputs(batch_data))

@@ -13,8 +13,14 @@ tests/test_prefetch.py.
         agent.update_parameters(sampler.next(), agent.update_step, i)
     sampler.close()
 
+A staging set is rewritten only after (a) the consumer has given the batch up -- by calling next() `outstanding` more times -- and
+(b) the `uploaded_event` the runtime hung on the batch dict, if it ever did, has completed.  The loop above holds one batch at
+a time (outstanding=1, the default); a loop that draws the next batch before it has passed the current one to update_parameters
+holds two (train_off_policy's lookahead: it draws ahead only from a sampler whose `max_outstanding` is None or >= 2).
+
 With a DeviceReplay (GPU-resident buffer) the handles of `sample_lazy` are prefetched instead (index vectors only).
 """
+import collections
 import queue
 import threading
 
@@ -26,8 +32,12 @@ KEYS = ("point_state_batch", "next_point_state_batch", "action_batch", "expert_a
 
 
 class PrefetchSampler(object):
-    def __init__(self, memory, batch_size, depth=2, rng=None, pin=None, sample=None, threads=4):
+    def __init__(self, memory, batch_size, depth=2, rng=None, pin=None, sample=None, threads=4, outstanding=1):
         """memory: BaseMemory (host sampling into pinned staging sets) or DeviceReplay (lazy gather handles).
+        outstanding: how many of the most recent minibatches handed out stay valid (`max_outstanding`).  1: next() gives the
+        previous batch's staging set back -- a loop that holds one batch at a time.  A loop that draws batch k+1 BEFORE it passes
+        batch k to update_parameters (train_off_policy's lookahead) holds two and needs outstanding=2; depth + outstanding sets
+        circulate.  Over a DeviceReplay `max_outstanding` is None: its handles own their staging until they are gathered.
         sample: optional callable(batch_size) -> batch dict replacing memory.sample (e.g. a validity-checking sampler); if it
         accepts `clouds_out` / `pool` keywords (BaseMemory.sample's, synth_data.sample_valid_batch's) the two cloud gathers --
         97 % of the bytes -- are written straight into the pinned staging set by `threads` pool threads (np.take releases the
@@ -35,6 +45,10 @@ class PrefetchSampler(object):
         self.memory, self.batch_size, self.depth = memory, int(batch_size), int(depth)
         self.rng = rng
         self.lazy = hasattr(memory, "sample_lazy")
+        if int(outstanding) < 1:
+            raise ValueError("PrefetchSampler(outstanding=%r): at least the batch next() returned stays valid" % (outstanding,))
+        self._outstanding = int(outstanding)
+        self.max_outstanding = None if self.lazy else self._outstanding
         self.pin = torch.cuda.is_available() if pin is None else bool(pin)
         self._sample = sample
         self._pool = None
@@ -52,7 +66,7 @@ class PrefetchSampler(object):
         self._free = queue.Queue()
         self._ready = queue.Queue(maxsize=self.depth)
         self._sets = []
-        self._held = self._held_item = None
+        self._held = collections.deque()         # (staging set, batch dict) of the batches handed out and not yet given up
         self._stop = threading.Event()
         self._error = None
         self._thread = threading.Thread(target=self._run, name="gad-prefetch", daemon=True)
@@ -73,7 +87,7 @@ class PrefetchSampler(object):
             return self.memory.sample(batch_size=self.batch_size)
 
     def _staging(self, batch):
-        """one pinned float32 staging set shaped like `batch` (allocated on first use: depth + 1 sets circulate)"""
+        """one pinned float32 staging set shaped like `batch` (allocated on first use: depth + outstanding sets circulate)"""
         st = {}
         for k in KEYS:
             if k in batch:
@@ -93,12 +107,12 @@ class PrefetchSampler(object):
 
     def _acquire(self, make):
         """a free staging set: one that came back from the consumer (after its upload event), a new one while fewer than
-        depth + 1 exist, else wait for one; None when the sampler is closing"""
+        depth + outstanding exist, else wait for one; None when the sampler is closing"""
         try:
             return self._release(self._free.get_nowait())
         except queue.Empty:
             pass
-        if len(self._sets) < self.depth + 1:
+        if len(self._sets) < self.depth + self._outstanding:
             st = make()
             self._sets.append(st)
             return st
@@ -111,9 +125,12 @@ class PrefetchSampler(object):
 
     @staticmethod
     def _release(entry):
-        """a staging set comes back with the event after which its host-to-device copies are done (the runtime hangs it on
-        the batch dict as `uploaded_event`; a run-ahead consumer may return the set before those copies have run)"""
-        st, ev = entry
+        """a staging set comes back with the batch dict it was handed out in: the runtime hangs the event after which its
+        host-to-device copies are done on that dict as `uploaded_event` (a run-ahead consumer may return the set before those
+        copies have run).  Read HERE, when the set is about to be rewritten, not when it came back: None then means the batch
+        was given up without ever being uploaded"""
+        st, item = entry
+        ev = item.get("uploaded_event")
         if ev is not None:
             ev.synchronize()
         return st
@@ -170,16 +187,17 @@ class PrefetchSampler(object):
 
     # ------------------------------------------------------------------ consumer
     def next(self):
-        """the next minibatch; the staging set handed out by the PREVIOUS call returns to the pool together with the event
-        that marks its host-to-device copies done (the producer waits for it before overwriting the set)"""
-        if self._held is not None:
-            self._free.put((self._held, self._held_item.get("uploaded_event")))
-            self._held = self._held_item = None
+        """the next minibatch.  The caller gives up the batch handed out `outstanding` calls ago: its staging set returns to the
+        pool with its batch dict, and the producer rewrites it only after that dict's `uploaded_event`, if the runtime ever set
+        one, has completed"""
+        while len(self._held) >= self._outstanding:
+            self._free.put(self._held.popleft())
         item = self._ready.get()
         if item is None:
             raise RuntimeError("prefetch thread failed") from self._error
-        self._held = item.pop("_staging", None) if isinstance(item, dict) else None
-        self._held_item = item if self._held is not None else None
+        st = item.pop("_staging", None) if isinstance(item, dict) else None
+        if st is not None:
+            self._held.append((st, item))
         return item
 
     __call__ = lambda self, batch_size=None: self.next()           # drop-in for memory.sample(batch_size=...)

@@ -100,6 +100,14 @@ def train_off_policy(agent, memory, config, model_output_dir=None, save_model=Fa
     config = cfg.RL_TRAIN (updates_per_step, batch_size, save_epoch, max_epoch).  `sample(batch_size)` overrides
     memory.sample (device-resident replay, prefetching samplers).  Returns the per-key loss history (deques, as the
     reference keeps them) and the number of epochs run.
+    The default loop HOLDS TWO MINIBATCHES AT ONCE: minibatch i + 1 is drawn (and handed to agent.prefetch) before minibatch i is
+    passed to update_parameters.  A `sample` callable must therefore return a batch that stays whole until the SECOND call after it:
+    fresh arrays or tensors per call (memory.sample, DeviceReplay.sample / sample_lazy), or buffers it does not reuse that early.
+    A callable that recycles its buffers says how many of its latest batches stay valid in an attribute `max_outstanding`
+    (PrefetchSampler(outstanding=...); None = any number): with a value below 2 the loop draws nothing ahead and holds one batch at a
+    time, as under GAD_TRAIN_LOOKAHEAD=0 and as run_ahead=True always does.  Under run_ahead a reused buffer must also not be
+    rewritten before the upload of the step that reads it has run: the runtime puts that event into batch["uploaded_event"] when
+    the batch dict has this key (PrefetchSampler waits for it).
     run_ahead: enqueue the `updates_per_step` updates of an epoch without waiting for each (update_parameters(sync=False));
     their losses are read at the end of the epoch, the host samples / stages the next minibatch while the GPU works.
     rng: a numpy Generator / RandomState for the minibatch indices of the mirrored path (default: the global np.random
@@ -151,6 +159,14 @@ def train_off_policy(agent, memory, config, model_output_dir=None, save_model=Fa
     # the sampler's random stream in between) and handed to agent.prefetch(), which stages its upload + geometry beside the
     # running update (device-resident minibatches; a no-op otherwise).
     lookahead = (not run_ahead) and hasattr(agent, "prefetch") and os.environ.get("GAD_TRAIN_LOOKAHEAD", "1") == "1"
+    # Drawn ahead, minibatch i + 1 exists while minibatch i has not been uploaded yet: a sampler that keeps only its latest batch
+    # valid (PrefetchSampler's default) would refill i's buffers under it.  Such a sampler says so, and is not drawn ahead from:
+    # its batches are host batches, which agent.prefetch() does not stage early anyway
+    keeps = getattr(sample, "max_outstanding", None)
+    if lookahead and keeps is not None and keeps < 2:
+        lookahead = False
+        if log is not None:
+            log("sample.max_outstanding = %d: one minibatch at a time, the next one is not drawn ahead (outstanding=2 allows it)" % keeps)
     ahead = None
 
     def is_last(epoch, i):

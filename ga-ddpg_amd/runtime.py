@@ -865,7 +865,10 @@ class FusedRuntime(object):
         ddpg_step(batch) -- the SAME batch object -- then starts from there.  This is what lets the reference-shaped loop
         (sample, update, read the losses, every iteration: core/train_test_offline.py:117-126) keep the GPU busy across its
         host synchronisation: core.train_test_offline.train_off_policy samples one minibatch ahead and calls this.
-        Device-resident minibatches only (DeviceReplay.sample_lazy, CUDA tensors); -> False when nothing was staged."""
+        Device-resident minibatches only (DeviceReplay.sample_lazy, CUDA tensors).  -> True when the hint was taken, which is not
+        "will be used": the staging is deferred to the end of the next step's enqueue (_finish_step), a step that is walked
+        (test=True) drops it there, and a step that then gets another batch object stages its own inputs (_take_inputs).
+        -> False when the hint was refused: walked or one-stream runtime, host batch, one input set."""
         if not self._replays() or engine.serial() or batch is None:
             return False
         dev_batch = "replay_gather" in batch or (torch.is_tensor(batch.get("point_state_batch")) and batch["point_state_batch"].is_cuda)
