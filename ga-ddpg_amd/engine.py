@@ -5,6 +5,12 @@ PointNet++ encoder, the actor/critic heads and their backward passes.
 Nothing here computes: every arithmetic step is a libgaddpg kernel (ga-ddpg_amd/hip.py).  torch
 only owns device memory and the stream.  A *plan* is a list of pre-built calls over static buffers.
 
+The launches of one stage of (conv, BatchNorm, ReLU) layers are spelled ONCE, in the emitters behind stage_view(): layer_input,
+fwd_gemm_args, emit_bn_finalize, emit_bn_eval_affine, emit_pool_finalize, emit_pool_bwd_stats, emit_bn_bwd_coef, bn_dz, prev_block,
+dx_args, dw_args.  The update step (plan_encoder_forward / plan_encoder_backward over encoder_views), the stand-alone module path
+(sa_function._StageRun.view) and the heads (heads.py) call them; what those callers differ in -- which launches are made, on which
+lane, under which tag and switch -- stays with the caller.
+
 Reference structure mirrored: core/networks.py:65-92 (base_network = SA1, SA2, SA3, FC head),
 :253-300 (QNetwork), :303-371 (GaussianPolicy); upstream PointnetSAModule.forward.
 """
@@ -13,6 +19,7 @@ import ctypes as C
 import os
 import struct
 import sys
+import types
 import weakref
 
 import numpy as np
@@ -246,9 +253,7 @@ class Geometry(object):
         self.rows = []
         self.rows_n = torch.zeros(4, **i32)        # live rows of SA1, SA2, SA3 side by side: one 8-byte D2H copy brings SA1 + SA2 to the host
         for s_, (G, cap) in enumerate(((B * M1, B * M1 * sa1.nsample), (B * M2, B * M2 * sa2.nsample), (B, B * M2))):
-            self.rows.append(dict(G=G, cap=cap, off=torch.zeros(G + 1, **i32), pt=torch.zeros(cap, **i32),
-                                  grp=torch.zeros(cap, **i32), w=torch.zeros(cap, **f32),
-                                  n=self.rows_n[s_:s_ + 1]))
+            self.rows.append(stage_rows(G, cap, device, n=self.rows_n[s_:s_ + 1]))
         r3 = self.rows[2]
         hip.call("gad_rows_group_all", B, M2, r3["off"], r3["pt"], r3["grp"], r3["w"], r3["n"])
         self.counts = (float(B * M1 * sa1.nsample), float(B * M2 * sa2.nsample), float(B * M2))
@@ -307,30 +312,10 @@ class EncoderNet(object):
         for i, m in enumerate(self.mats):
             m.bn_index = i
         self.flat = FlatNet(list(module.named_parameters()), self.mats, device)
-        # split-bf16 mirrors: every SA layer behind a BatchNorm + ReLU (K = the channel count) and the gathered first layers of
-        # SA2 / SA3 (their feature columns; the three coordinate columns stay a rank-3 f32 update)
-        self.flat.enable_split([(m, (m.gather_feat_c if l == 0 else m.Kp)) for st in self.sa_mats for l, m in enumerate(st)
-                                if (l > 0 or m.gather_feat_c >= 32)])
+        self.flat.enable_split([x for st in self.sa_mats for x in split_mirror_layers(st)])
         self.c_feat = self.sa_mats[0][0].k_in - 3              # 4 (policy) or 10 (critic: + 6 action channels)
         self.act_c = self.c_feat - 4
-        # BatchNorm running statistics: one flat buffer per kind, module buffers become views
-        tot = sum(m.n_out for m in self.mats)
-        self.running_mean = torch.zeros(tot, dtype=torch.float32, device=device)
-        self.running_var = torch.ones(tot, dtype=torch.float32, device=device)
-        self.bn_off = []
-        self.batches_tracked = torch.zeros(len(self.mats), dtype=torch.int64, device=device)
-        o = 0
-        for i_m, m in enumerate(self.mats):
-            self.bn_off.append(o)
-            with torch.no_grad():
-                self.running_mean[o:o + m.n_out].copy_(m.bn.running_mean.to(device))
-                self.running_var[o:o + m.n_out].copy_(m.bn.running_var.to(device))
-            m.bn.running_mean = self.running_mean[o:o + m.n_out]
-            m.bn.running_var = self.running_var[o:o + m.n_out]
-            self.batches_tracked[i_m] = int(m.bn.num_batches_tracked)
-            m.bn.num_batches_tracked = self.batches_tracked[i_m]      # 0-d view of the flat counter buffer
-            o += m.n_out
-        self.bn_total = tot
+        self.running_mean, self.running_var, self.batches_tracked, self.bn_off, self.bn_total = adopt_running_stats(self.mats, device)
 
     def bump_batches_tracked(self, k=1):
         self.batches_tracked += k           # one launch for all BatchNorm counters of the encoder
@@ -936,72 +921,248 @@ def timing_routes():
 
 
 # ----------------------------------------------------------------------------------------------
-# encoder forward / backward plans
+# one stage of (conv, BatchNorm, ReLU) layers: its view and the ONE spelling of each of its launches
 # ----------------------------------------------------------------------------------------------
 def _bn_vec(slot, enc, m, which):
     return _ptr(getattr(slot, which), enc.bn_off[m.bn_index])
 
 
-def _finalize(plan, enc, slot, m, count, train=True, update_running=True):
-    o, tot = enc.bn_off[m.bn_index], slot.tot
-    if not train:        # eval mode: affine from the running statistics (torch BatchNorm eval semantics)
-        plan.call("gad_bn_eval_affine", enc.flat.p_gamma(m), enc.flat.p_beta(m), _ptr(enc.running_mean, o),
-                  _ptr(enc.running_var, o), m.n_out, BN_EPS, _bn_vec(slot, enc, m, "scale"), _bn_vec(slot, enc, m, "shift"))
-        return
-    plan.call("gad_bn_finalize", _ptr(slot.stats, o, 8), _ptr(slot.stats, tot + o, 8), 2 * tot, enc.flat.p_gamma(m),
-              enc.flat.p_beta(m), m.n_out, hip.Dbl(count), BN_EPS, BN_MOMENTUM,
-              _ptr(enc.running_mean, o) if update_running else None, _ptr(enc.running_var, o) if update_running else None,
-              _bn_vec(slot, enc, m, "scale"), _bn_vec(slot, enc, m, "shift"), _bn_vec(slot, enc, m, "mean"),
-              _bn_vec(slot, enc, m, "istd"))
+def adopt_running_stats(mats, device):
+    """the BatchNorm running statistics of `mats` in one flat buffer per kind: the modules' buffers become views of them
+    (num_batches_tracked a 0-d view of the counter buffer) -> (running_mean, running_var, batches_tracked, bn_off, total)"""
+    tot = sum(m.n_out for m in mats)
+    mean = torch.zeros(tot, dtype=torch.float32, device=device)
+    var = torch.ones(tot, dtype=torch.float32, device=device)
+    tracked = torch.zeros(len(mats), dtype=torch.int64, device=device)
+    bn_off, o = [], 0
+    for i, m in enumerate(mats):
+        bn_off.append(o)
+        with torch.no_grad():
+            mean[o:o + m.n_out].copy_(m.bn.running_mean.to(device))
+            var[o:o + m.n_out].copy_(m.bn.running_var.to(device))
+        m.bn.running_mean, m.bn.running_var = mean[o:o + m.n_out], var[o:o + m.n_out]
+        tracked[i] = int(m.bn.num_batches_tracked)
+        m.bn.num_batches_tracked = tracked[i]
+        o += m.n_out
+    return mean, var, tracked, bn_off, tot
 
 
-def _gather_src(geo, slot, s, action):
-    """input description of SA stage s's first layer"""
-    r = geo.rows[s]
-    if s == 0:
-        return dict(src_xyz=_ptr(geo.xyz), ctr_xyz=_ptr(geo.new_xyz1), feat=_ptr(geo.feat0), feat_c=4,
-                    action=_ptr(action), act_c=6 if action is not None else 0, grp_per_sample=geo.M1,
-                    row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]))
-    if s == 1:
-        return dict(src_xyz=_ptr(geo.new_xyz1), ctr_xyz=_ptr(geo.new_xyz2), feat=_ptr(slot.F[0]),
-                    feat_c=slot.F[0].shape[1], action=None, act_c=0, grp_per_sample=geo.M2,
-                    row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]))
-    return dict(src_xyz=_ptr(geo.new_xyz2), ctr_xyz=None, feat=_ptr(slot.F[1]), feat_c=slot.F[1].shape[1],
-                action=None, act_c=0, grp_per_sample=1, row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]))
+def split_mirror_layers(stage):
+    """[(MatSpec, Ks)] for FlatNet.enable_split: every layer of an SA stage behind a BatchNorm + ReLU (K = the channel count) and
+    a gathered first layer with 32 or more feature columns (those columns; the coordinate columns stay a rank-3 f32 update)"""
+    return [(m, (m.gather_feat_c if l == 0 else m.Kp)) for l, m in enumerate(stage) if l > 0 or m.gather_feat_c >= 32]
 
 
-def _layer_input(enc, slot, geo, s, l, action, fin=None, forward=False):
-    """gad_gemm_fwd_args fields describing the INPUT of SA stage s layer l (s==3: FC layer l).
-    fin = (count, update_running): the input layer's train-mode BatchNorm is finalised by THIS launch (gad_gemm_fwd_args
-    in_*: no gad_bn_finalize launch between the two GEMMs)"""
-    if s < 3:
-        r = geo.rows[s]
-        base = dict(n_rows_dev=_ptr(r["n"]), n_rows=r["cap"], row_w=_ptr(r["w"]))
-        if l == 0:
-            base.update(mode=1, c_in=enc.sa_mats[s][0].k_in, **_gather_src(geo, slot, s, action))
-        else:
-            pm = enc.sa_mats[s][l - 1]
-            base.update(mode=0, zin=_ptr(slot.Z[s][l - 1]), zin_pitch=pm.n_out, c_in=pm.n_out,
-                        scale=_bn_vec(slot, enc, pm, "scale"), shift=_bn_vec(slot, enc, pm, "shift"), relu=1)
-            if forward and recomputed_input(enc, geo, s, l):       # (the backward pass reads the stored z1)
-                # layer 1's output is recomputed from the gathered rows inside this launch (bit-equal to what layer 1 stored)
-                base.update(mode=2, pre_W=enc.flat.p_w(pm), pre_Kp=pm.Kp, **_gather_src(geo, slot, s, action))
-            if fin is not None:
-                base.update(_input_bn(enc, slot, pm, fin))
-        return base
-    B = slot.B
-    if l == 0:
-        return dict(n_rows=B, mode=0, zin=_ptr(slot.F[2]), zin_pitch=slot.F[2].shape[1], c_in=slot.F[2].shape[1],
-                    relu=0, ones_col=enc.fc_mats[0].ones_col)
-    pm = enc.fc_mats[0]
-    base = dict(n_rows=B, mode=0, zin=_ptr(slot.Zfc[0]), zin_pitch=pm.n_out, c_in=pm.n_out,
-                scale=_bn_vec(slot, enc, pm, "scale"), shift=_bn_vec(slot, enc, pm, "shift"), relu=1,
-                ones_col=enc.fc_mats[1].ones_col)
-    if fin is not None:
-        base.update(_input_bn(enc, slot, pm, fin))
-    return base
+def stage_rows(G, cap, device, n=None):
+    """the row-list buffers of a stage of G groups and at most cap rows; n: where its live-row count is kept (default: its own)"""
+    i32 = dict(dtype=torch.int32, device=device)
+    return dict(G=G, cap=cap, off=torch.zeros(G + 1, **i32), pt=torch.zeros(cap, **i32), grp=torch.zeros(cap, **i32),
+                w=torch.zeros(cap, dtype=torch.float32, device=device), n=torch.zeros(1, **i32) if n is None else n)
 
 
+def stage_view(bufs, mats, bn_off, **fields):
+    """What the emitters below read of one stage: the per-pass BatchNorm vectors of `bufs` (an EncoderSlot, a
+    sa_function._StageRun: stats, bstats, coef, scale, shift, mean, istd, tot), the layers' MatSpecs with their offsets into those
+    vectors, and as `fields`: rows (stage_rows; None = B dense rows: the FC pair), Z, F, argmax, key, zmax, count, G (the dY pair),
+    dF, and the gather source of the first layer: src_xyz, ctr_xyz, feat, feat_c, action, act_c, grp_per_sample"""
+    v = types.SimpleNamespace(mats=mats, bn_off=bn_off, **fields)
+    for k in ("stats", "bstats", "coef", "scale", "shift", "mean", "istd", "tot"):
+        setattr(v, k, getattr(bufs, k, None))
+    return v
+
+
+def encoder_views(enc, slot, action=None):
+    """the stage views of one encoder pass: SA1, SA2, SA3 and the FC pair (its `feat` = the pooled SA3 features)"""
+    geo = slot.geo
+    xyz = (geo.xyz, geo.new_xyz1, geo.new_xyz2, None)
+    feat = (geo.feat0, slot.F[0], slot.F[1], slot.F[2])
+    bwd = lambda name, s: getattr(slot, name)[s] if slot.with_backward else None
+    views = []
+    for s, mats in enumerate(enc.sa_mats):
+        views.append(stage_view(slot, mats, [enc.bn_off[m.bn_index] for m in mats], rows=geo.rows[s], Z=slot.Z[s], F=slot.F[s],
+                                argmax=slot.argmax[s], key=slot.key[s], zmax=slot.zmax[s], count=geo.counts[s], G=bwd("G", s),
+                                dF=bwd("dF", s), src_xyz=xyz[s], ctr_xyz=xyz[s + 1], feat=feat[s], feat_c=feat[s].shape[1],
+                                action=action if s == 0 else None, act_c=6 if (s == 0 and action is not None) else 0,
+                                grp_per_sample=(geo.M1, geo.M2, 1)[s]))
+    views.append(stage_view(slot, enc.fc_mats, [enc.bn_off[m.bn_index] for m in enc.fc_mats], rows=None, B=slot.B, Z=slot.Zfc,
+                            count=float(slot.B), feat=feat[3], feat_c=feat[3].shape[1]))
+    return views
+
+
+def _vec(v, which, l):
+    return _ptr(getattr(v, which), v.bn_off[l])
+
+
+def _sums(v, which, l):
+    """the two f64 sum vectors of layer l in v.stats / v.bstats ([sum | sq], [dbeta | dgamma])"""
+    return _ptr(getattr(v, which), v.bn_off[l], 8), _ptr(getattr(v, which), v.tot + v.bn_off[l], 8)
+
+
+def _gather_src(v):
+    r = v.rows
+    return dict(src_xyz=_ptr(v.src_xyz), ctr_xyz=_ptr(v.ctr_xyz), feat=_ptr(v.feat), feat_c=v.feat_c, action=_ptr(v.action),
+                act_c=v.act_c, grp_per_sample=v.grp_per_sample, row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]))
+
+
+def layer_input(net, v, l, in_bn=None, recompute=False):
+    """gad_gemm_fwd_args fields describing the INPUT of layer l of view v.
+    in_bn = update_running (True / False): the input layer's train-mode BatchNorm is finalised by THIS launch (in_*: no
+    gad_bn_finalize launch between the two GEMMs).  recompute: the input layer's output is recomputed from the gathered rows inside
+    this launch (gad_gemm_fwd mode 2; bit-equal to what that layer stored)"""
+    r = v.rows
+    if r is None:
+        kw = dict(n_rows=v.B, ones_col=v.mats[l].ones_col)
+    else:
+        kw = dict(n_rows_dev=_ptr(r["n"]), n_rows=r["cap"], row_w=_ptr(r["w"]))
+    if l == 0 and r is None:            # FC 1 reads the pooled features as they are
+        kw.update(mode=0, zin=_ptr(v.feat), zin_pitch=v.feat_c, c_in=v.feat_c, relu=0)
+    elif l == 0:
+        kw.update(mode=1, c_in=v.mats[0].k_packed, **_gather_src(v))
+    else:
+        pm = v.mats[l - 1]
+        kw.update(mode=0, zin=_ptr(v.Z[l - 1]), zin_pitch=pm.n_out, c_in=pm.n_out, scale=_vec(v, "scale", l - 1),
+                  shift=_vec(v, "shift", l - 1), relu=1)
+        if recompute:
+            kw.update(mode=2, pre_W=net.flat.p_w(pm), pre_Kp=pm.Kp, **_gather_src(v))
+        if in_bn is not None:
+            s1, s2 = _sums(v, "stats", l - 1)
+            kw.update(in_stat_sum=s1, in_stat_sq=s2, in_stat_stride=2 * v.tot, in_count=float(v.count),
+                      in_gamma=net.flat.p_gamma(pm), in_beta=net.flat.p_beta(pm), in_eps=BN_EPS, in_momentum=BN_MOMENTUM,
+                      in_running_mean=_ptr(net.running_mean, v.bn_off[l - 1]) if in_bn else None,
+                      in_running_var=_ptr(net.running_var, v.bn_off[l - 1]) if in_bn else None,
+                      in_mean=_vec(v, "mean", l - 1), in_istd=_vec(v, "istd", l - 1))
+    return kw
+
+
+def fwd_gemm_args(net, v, l, zout, stats=True, pooled=False, **input_flags):
+    """the gad_gemm_fwd struct of layer l: input (layer_input), weights with their split mirror, raw output, the f64 statistics
+    (stats) and the packed arg-max keys of a max-pool folded into the epilogue (pooled)"""
+    m = v.mats[l]
+    kw = layer_input(net, v, l, **input_flags)
+    if pooled:
+        kw.update(pool_key=_ptr(v.key, 0, 8), pool_row_grp=_ptr(v.rows["grp"]), pool_gamma=net.flat.p_gamma(m))
+    kw.update(net.flat.split_fwd_kw(m))
+    s1, s2 = _sums(v, "stats", l) if stats else (None, None)
+    return _fwd_args(W=net.flat.p_w(m), Kp=m.Kp, n_out=[m.n_out], zout=_ptr(zout), zout_pitch=m.n_out, stat_sum=s1, stat_sq=s2,
+                     stat_stride=2 * v.tot, **kw)
+
+
+def _running(net, v, l, update):
+    o = v.bn_off[l]
+    return (_ptr(net.running_mean, o), _ptr(net.running_var, o)) if update else (None, None)
+
+
+def emit_bn_finalize(plan, net, v, l, update_running=True):
+    """train-mode BatchNorm of layer l from its statistics: scale / shift / mean / istd, momentum update of the running buffers"""
+    m = v.mats[l]
+    plan.call("gad_bn_finalize", *_sums(v, "stats", l), 2 * v.tot, net.flat.p_gamma(m), net.flat.p_beta(m), m.n_out,
+              hip.Dbl(v.count), BN_EPS, BN_MOMENTUM, *_running(net, v, l, update_running), _vec(v, "scale", l), _vec(v, "shift", l),
+              _vec(v, "mean", l), _vec(v, "istd", l))
+
+
+def emit_bn_eval_affine(plan, net, v, l):
+    """eval mode: scale / shift from the running statistics (torch BatchNorm eval semantics)"""
+    m = v.mats[l]
+    plan.call("gad_bn_eval_affine", net.flat.p_gamma(m), net.flat.p_beta(m), *_running(net, v, l, True), m.n_out, BN_EPS,
+              _vec(v, "scale", l), _vec(v, "shift", l))
+
+
+def emit_pool_finalize(plan, net, v, train, update_running=True):
+    """finalises the pooled (third) layer's train-mode BatchNorm (same arithmetic and outputs as gad_bn_finalize) or takes the
+    eval-mode scale / shift as given, then turns the packed keys into pooled features, arg-max rows and their raw values"""
+    m, r = v.mats[2], v.rows
+    stats = (*_sums(v, "stats", 2), 2 * v.tot, hip.Dbl(v.count)) if train else (None, None, 0, hip.Dbl(1.0))
+    plan.call("gad_pool_finalize", _ptr(v.key, 0, 8), m.n_out, r["G"], r["off"], *stats, net.flat.p_gamma(m), net.flat.p_beta(m),
+              BN_EPS, BN_MOMENTUM, *_running(net, v, 2, train and update_running), _vec(v, "scale", 2), _vec(v, "shift", 2),
+              _vec(v, "mean", 2), _vec(v, "istd", 2), v.F, v.argmax, v.zmax)
+
+
+def emit_pool_bwd_stats(plan, v):
+    """dbeta / dgamma of the pooled layer; the pooled gradient v.dF is ReLU-masked in place for its consumers"""
+    m = v.mats[2]
+    plan.call("gad_pool_bwd_stats", v.dF, v.argmax, v.rows["G"], m.n_out, v.Z[2], m.n_out, _vec(v, "scale", 2), _vec(v, "shift", 2),
+              _vec(v, "mean", 2), _vec(v, "istd", 2), *_sums(v, "bstats", 2), 2 * v.tot, 1, v.zmax)
+
+
+def _coef_ptrs(v, l):
+    o, tot = v.bn_off[l], v.tot
+    return _ptr(v.coef, o), _ptr(v.coef, tot + o), _ptr(v.coef, 2 * tot + o)
+
+
+def _arena_bn(net, m, on=True):
+    """layer m's dgamma / dbeta slots of the f64 gradient arena"""
+    return (_ptr(net.flat.gacc, m.g_off, 8), _ptr(net.flat.gacc, m.b_off, 8)) if on else (None, None)
+
+
+def emit_bn_bwd_coef(plan, net, v, l, count, accumulate=True):
+    """BatchNorm-backward coefficients P, Q, S of layer l from its dbeta / dgamma sums; accumulate: adds dgamma / dbeta to the arena"""
+    m = v.mats[l]
+    plan.call("gad_bn_bwd_coef", *_sums(v, "bstats", l), 2 * v.tot, _vec(v, "scale", l), _vec(v, "mean", l), _vec(v, "istd", l),
+              m.n_out, hip.Dbl(count), *_coef_ptrs(v, l), *_arena_bn(net, m, accumulate))
+
+
+def bn_dz(net, v, l, G=None, pooled=False, inline_count=None, accumulate=False):
+    """the dZ descriptor of BatchNorm + ReLU layer l: dY from G (premasked by the producing dX) or, pooled, routed from v.dF through
+    the arg-max.  inline_count: P, Q, S are formed in the consuming launch's prologue (no gad_bn_bwd_coef launch) with this count,
+    and the launch given `accumulate` adds dgamma / dbeta to the gradient arena"""
+    m, r = v.mats[l], v.rows
+    d = dict(z=_ptr(v.Z[l]), z_pitch=m.n_out, scale=_vec(v, "scale", l), shift=_vec(v, "shift", l), relu=1, premasked=1,
+             row_w=_ptr(r["w"]) if r is not None else None, c=m.n_out)
+    d["coefP"], d["coefQ"], d["coefS"] = _coef_ptrs(v, l)
+    if inline_count is not None:
+        d["bn_dbeta"], d["bn_dgamma"] = _sums(v, "bstats", l)
+        d.update(bn_stride=2 * v.tot, bn_count=float(inline_count), bn_mean=_vec(v, "mean", l), bn_istd=_vec(v, "istd", l))
+        d["gacc_gamma"], d["gacc_beta"] = _arena_bn(net, m, accumulate)
+    if pooled:
+        d.update(gmode=1, argmax=_ptr(v.argmax), dout=_ptr(v.dF), row_grp=_ptr(r["grp"]))
+    else:
+        d.update(gmode=0, G=_ptr(G), g_pitch=m.n_out)
+    return _dz(**d)
+
+
+def prev_block(v, l):
+    """gad_gemm_dx_args prev_*: the dX launch masks its output by layer l's ReLU and sums that layer's dbeta / dgamma"""
+    pm = v.mats[l]
+    dbeta, dgamma = _sums(v, "bstats", l)
+    return dict(zprev=_ptr(v.Z[l]), zprev_pitch=pm.n_out, prev_scale=_vec(v, "scale", l), prev_shift=_vec(v, "shift", l),
+                prev_mean=_vec(v, "mean", l), prev_istd=_vec(v, "istd", l), prev_dbeta=dbeta, prev_dgamma=dgamma,
+                stat_stride=2 * v.tot, store_masked=1)
+
+
+def dx_args(fl, dz, m, k_valid, n_rows, n_rows_dev=None, groups=None, **epi):
+    """the gad_gemm_dx struct over matrix m of FlatNet fl.  groups = [(MatSpec, dz_off, gout_off)]: the grouped form (blockIdx.z =
+    group) over the whole packed buffer, every group's weights at its w_off; `epi`: the epilogue fields as they are"""
+    a = hip.GemmDxArgs()
+    a.n_rows_dev, a.n_rows, a.dz = n_rows_dev, n_rows, dz
+    a.Kp, a.k_valid, a.grp_per_sample = m.Kp, k_valid, 1
+    if groups is None:
+        a.n_groups, a.W = 1, fl.p_w(m)
+        a.n_out[0] = m.n_out
+    else:
+        a.n_groups, a.W = len(groups), _ptr(fl.packed)
+        for i, (g, dz_off, gout_off) in enumerate(groups):
+            a.dz_off[i], a.w_off[i], a.n_out[i], a.gout_off[i] = dz_off, g.w_off, g.n_out, gout_off
+    for k, x in dict(epi, **fl.split_t_kw(m)).items():
+        setattr(a, k, x)
+    return a
+
+
+def dw_args(fl, mats, inp, dz, ws, dz_off=()):
+    """the gad_gemm_dw struct: `mats` = the groups' matrices, inp = the gad_gemm_fwd_args fields of the layer's input, ws = the
+    split-K workspace of the lane the launch runs on, dz_off = the groups' column offsets into dZ"""
+    a = hip.GemmDwArgs()
+    a.inp = _fwd_args(Kp=mats[0].Kp, n_groups=len(mats), w_off=[m.w_off for m in mats], n_out=[m.n_out for m in mats], **inp)
+    a.dz = dz
+    for i, o in enumerate(dz_off):
+        a.dz_off[i] = o
+    a.gacc = _ptr(fl.gacc)
+    a.partial, a.partial_elems = _ptr(ws), ws.numel()
+    return a
+
+
+# ----------------------------------------------------------------------------------------------
+# encoder forward / backward plans
+# ----------------------------------------------------------------------------------------------
 def recomputed_input(enc, geo, s, l):
     """SA1 layer 2 on the streaming kernel's shapes: gad_gemm_fwd mode 2"""
     if not (RECOMP_SA1 and s == 0 and l == 1):
@@ -1012,16 +1173,6 @@ def recomputed_input(enc, geo, s, l):
         raise RuntimeError("GAD_RECOMP_SA1=1 needs GAD_OPT_mfma_split=0 (the recomputing SA1 launch has no split-bf16 form)")
     m0, m1 = enc.sa_mats[0][0], enc.sa_mats[0][1]
     return m0.n_out == 64 and m1.n_out == 64 and m1.Kp == 64 and m0.Kp in (8, 16) and geo.rows[0]["cap"] >= 32768
-
-
-def _input_bn(enc, slot, pm, fin):
-    """gad_gemm_fwd_args in_* block: layer pm's train-mode BatchNorm, finalised by the launch that consumes its output"""
-    o, tot = enc.bn_off[pm.bn_index], slot.tot
-    return dict(in_stat_sum=_ptr(slot.stats, o, 8), in_stat_sq=_ptr(slot.stats, tot + o, 8), in_stat_stride=2 * tot,
-                in_count=float(fin[0]), in_gamma=enc.flat.p_gamma(pm), in_beta=enc.flat.p_beta(pm), in_eps=BN_EPS,
-                in_momentum=BN_MOMENTUM, in_running_mean=_ptr(enc.running_mean, o) if fin[1] else None,
-                in_running_var=_ptr(enc.running_var, o) if fin[1] else None,
-                in_mean=_bn_vec(slot, enc, pm, "mean"), in_istd=_bn_vec(slot, enc, pm, "istd"))
 
 
 def plan_running_update(enc, slot):
@@ -1053,7 +1204,7 @@ def plan_encoder_forward(enc, slot, action=None, train=True, update_running=True
     geo = slot.geo
     plan = Plan()
     plan.zero(slot.stats)
-    tot = slot.tot
+    views = encoder_views(enc, slot, action)
     if not train and slot.with_backward:
         # eval-mode BatchNorm under a training step (update_parameters(test=True), reference core/agent.py:276-280): the backward
         # pass normalises with the RUNNING statistics too -- the vectors it reads as the layers' mean / inverse deviation
@@ -1069,62 +1220,36 @@ def plan_encoder_forward(enc, slot, action=None, train=True, update_running=True
             return DEFER_BN_WIDE and train and 3 in DEFER_BN_STAGES and l == 0      # FC 1, finalised by FC 2 (skinny kernel)
         return DEFER_BN_WIDE and train and s in DEFER_BN_STAGES and l < 2
 
-    def gemm(m, zout, s, l, tag, pool=None):
-        o = enc.bn_off[m.bn_index]
-        fin = ((geo.counts[s] if s < 3 else float(slot.B)), update_running) if (l > 0 and deferred(s, l - 1)) else None
-        kw = _layer_input(enc, slot, geo, s, l, action, fin=fin, forward=True)
-        if pool is not None:
-            kw.update(pool_key=_ptr(slot.key[s], 0, 8), pool_row_grp=_ptr(geo.rows[s]["grp"]), pool_gamma=enc.flat.p_gamma(m))
+    def gemm(s, l, tag):
+        zout = views[s].Z[l]
         if s == 0 and l == 0 and not slot.with_backward and recomputed_input(enc, geo, 0, 1):
             zout = None         # statistics only: layer 2 recomputes this output and nothing else reads it in a forward-only pass
-        kw.update(enc.flat.split_fwd_kw(m))
-        a = _fwd_args(W=enc.flat.p_w(m), Kp=m.Kp, n_out=[m.n_out], zout=_ptr(zout), zout_pitch=m.n_out,
-                      stat_sum=_ptr(slot.stats, o, 8), stat_sq=_ptr(slot.stats, tot + o, 8), stat_stride=2 * tot, **kw)
+        a = fwd_gemm_args(enc, views[s], l, zout, pooled=s < 3 and l == 2, recompute=l > 0 and recomputed_input(enc, geo, s, l),
+                          in_bn=update_running if (l > 0 and deferred(s, l - 1)) else None)
         if s < 2:
             plan.call("gad_grid_rows_hint", hip.Ptr(geo.rows_hint.ctypes.data + 4 * s))
         plan.call_struct("gad_gemm_fwd", a)
         plan.tag_last(tag)
 
-    def pool_finalize(s, m, count):
-        o = enc.bn_off[m.bn_index]
-        r = geo.rows[s]
-        if train:
-            stats = (_ptr(slot.stats, o, 8), _ptr(slot.stats, tot + o, 8), 2 * tot, hip.Dbl(count))
-            run = (_ptr(enc.running_mean, o), _ptr(enc.running_var, o)) if update_running else (None, None)
-        else:           # eval mode: scale / shift from the running statistics, computed before the keys are decoded
-            _finalize(plan, enc, slot, m, 0.0, False)
-            stats, run = (None, None, 0, hip.Dbl(1.0)), (None, None)
-        plan.call("gad_pool_finalize", _ptr(slot.key[s], 0, 8), m.n_out, r["G"], r["off"], *stats, enc.flat.p_gamma(m),
-                  enc.flat.p_beta(m), BN_EPS, BN_MOMENTUM, *run, _bn_vec(slot, enc, m, "scale"), _bn_vec(slot, enc, m, "shift"),
-                  _bn_vec(slot, enc, m, "mean"), _bn_vec(slot, enc, m, "istd"), slot.F[s], slot.argmax[s], slot.zmax[s])
-        plan.tag_last("pool.sa%d" % (s + 1))
+    def finalize(s, l):
+        if not train:
+            emit_bn_eval_affine(plan, enc, views[s], l)
+        elif not (l < 2 and deferred(s, l)):
+            emit_bn_finalize(plan, enc, views[s], l, update_running)
 
     for s in range(3):
-        for l, m in enumerate(enc.sa_mats[s]):
-            gemm(m, slot.Z[s][l], s, l, "fwd.sa%d.l%d" % (s + 1, l + 1), pool=(s if l == 2 else None))
-            if l < 2 and not deferred(s, l):
-                _finalize(plan, enc, slot, m, geo.counts[s], train, update_running)
-        pool_finalize(s, enc.sa_mats[s][2], geo.counts[s])
-    for l, m in enumerate(enc.fc_mats):
-        gemm(m, slot.Zfc[l], 3, l, "fwd.fc%d" % (l + 1))
-        if not deferred(3, l):
-            _finalize(plan, enc, slot, m, float(slot.B), train, update_running)
+        for l in range(3):
+            gemm(s, l, "fwd.sa%d.l%d" % (s + 1, l + 1))
+            if l < 2:
+                finalize(s, l)
+        if not train:           # eval mode: scale / shift from the running statistics, computed before the keys are decoded
+            emit_bn_eval_affine(plan, enc, views[s], 2)
+        emit_pool_finalize(plan, enc, views[s], train, update_running)
+        plan.tag_last("pool.sa%d" % (s + 1))
+    for l in range(2):
+        gemm(3, l, "fwd.fc%d" % (l + 1))
+        finalize(3, l)
     return plan
-
-
-def _coef_ptrs(slot, enc, m):
-    o, tot = enc.bn_off[m.bn_index], slot.tot
-    return _ptr(slot.coef, o), _ptr(slot.coef, tot + o), _ptr(slot.coef, 2 * tot + o)
-
-
-def _bn_coef(plan, enc, slot, m, count, want_dw):
-    o, tot = enc.bn_off[m.bn_index], slot.tot
-    P, Q, S = _coef_ptrs(slot, enc, m)
-    gacc = enc.flat.gacc
-    plan.call("gad_bn_bwd_coef", _ptr(slot.bstats, o, 8), _ptr(slot.bstats, tot + o, 8), 2 * tot,
-              _bn_vec(slot, enc, m, "scale"), _bn_vec(slot, enc, m, "mean"), _bn_vec(slot, enc, m, "istd"),
-              m.n_out, hip.Dbl(count), P, Q, S, _ptr(gacc, m.g_off, 8) if want_dw else None,
-              _ptr(gacc, m.b_off, 8) if want_dw else None)
 
 
 def plan_encoder_backward(enc, slot, g_fc2, action=None, want_dw=True, want_daction=False, dw_lane=1, zero_scatter=True,
@@ -1143,59 +1268,25 @@ def plan_encoder_backward(enc, slot, g_fc2, action=None, want_dw=True, want_dact
     geo = slot.geo
     plan = Plan()
     B = slot.B
-    tot = slot.tot
+    fl = enc.flat
+    views = encoder_views(enc, slot, action)
     # train=False: the backward of EVAL-mode BatchNorm (y = scale * z + shift with constants from the running statistics):
     # dZ = scale * dY, no batch-statistics terms.  The coefficient kernels form Q and S as (sums) / count, so an infinite count gives
     # exactly that (P = scale, Q = S = 0) through the same launches; dgamma / dbeta are the same sums as in train mode, taken with the
     # running mean / inverse deviation that plan_encoder_forward(train=False) put into slot.mean / slot.istd
     INF = float("inf")
-    n_fc = float(B) if train else INF
 
-    def prev_stats(pm, zprev):
-        o = enc.bn_off[pm.bn_index]
-        return dict(zprev=_ptr(zprev), zprev_pitch=pm.n_out, prev_scale=_bn_vec(slot, enc, pm, "scale"),
-                    prev_shift=_bn_vec(slot, enc, pm, "shift"), prev_mean=_bn_vec(slot, enc, pm, "mean"),
-                    prev_istd=_bn_vec(slot, enc, pm, "istd"), prev_dbeta=_ptr(slot.bstats, o, 8),
-                    prev_dgamma=_ptr(slot.bstats, tot + o, 8), stat_stride=2 * tot, store_masked=1)
-
-    def bn_dz(m, z, count, accumulate, G=None, pooled=None, row_w=None, inline=False):
-        d = dict(z=_ptr(z), z_pitch=m.n_out, scale=_bn_vec(slot, enc, m, "scale"),
-                 shift=_bn_vec(slot, enc, m, "shift"), relu=1, premasked=1, row_w=row_w, c=m.n_out)
-        d["coefP"], d["coefQ"], d["coefS"] = _coef_ptrs(slot, enc, m)
-        if inline:
-            # P, Q, S formed in the consuming launch's prologue (no gad_bn_bwd_coef launch); the launch given `accumulate` adds
-            # dgamma / dbeta to the gradient arena
-            o = enc.bn_off[m.bn_index]
-            d.update(bn_dbeta=_ptr(slot.bstats, o, 8), bn_dgamma=_ptr(slot.bstats, tot + o, 8), bn_stride=2 * tot, bn_count=float(count),
-                     bn_mean=_bn_vec(slot, enc, m, "mean"), bn_istd=_bn_vec(slot, enc, m, "istd"))
-            if accumulate and want_dw:
-                d.update(gacc_gamma=_ptr(enc.flat.gacc, m.g_off, 8), gacc_beta=_ptr(enc.flat.gacc, m.b_off, 8))
-        if pooled is None:
-            d.update(gmode=0, G=_ptr(G), g_pitch=m.n_out)
-        else:
-            d.update(gmode=1, argmax=_ptr(pooled[0]), dout=_ptr(pooled[1]), row_grp=_ptr(pooled[2]))
-        return _dz(**d)
-
-    def dx(rows_kw, dz, m, k_valid, **epi):
-        a = hip.GemmDxArgs()
-        a.n_rows_dev = rows_kw.get("n_rows_dev")
-        a.n_rows = rows_kw["n_rows"]
-        a.dz = dz
-        a.n_groups = 1
-        a.n_out[0] = m.n_out
-        a.W = enc.flat.p_w(m)
-        a.Kp = m.Kp
-        a.k_valid = k_valid
-        a.grp_per_sample = 1
-        for k, v in dict(epi, **enc.flat.split_t_kw(m)).items():
-            setattr(a, k, v)
-        stage = {"sa1": 0, "sa2": 1}.get(rows_kw.get("name"))
-        if stage is not None:
-            plan.call("gad_grid_rows_hint", hip.Ptr(geo.rows_hint.ctypes.data + 4 * stage))
+    def dx(s, l, dz, k_valid, **epi):
+        v = views[s]
+        name = "sa%d" % (s + 1) if s < 3 else "fc"
+        r = v.rows or dict(n=None, cap=B)
+        a = dx_args(fl, dz, v.mats[l], k_valid, r["cap"], _ptr(r["n"]), **epi)
+        if s < 2:
+            plan.call("gad_grid_rows_hint", hip.Ptr(geo.rows_hint.ctypes.data + 4 * s))
         if fused_dw:                       # dX and dW in one pass on this stream (gad_gemm_bwd): SA1 l3 / l2, SA2, SA3
             aw = fused_dw.pop()
             plan.call("gad_gemm_bwd", a, aw)
-            plan.tag_last("bwd.%s.l%d" % (rows_kw.get("name", "fc"), rows_kw.get("layer", 0)))
+            plan.tag_last("bwd.%s.l%d" % (name, l + 1))
             if aw.row_splits == DW_REDUCE_LATER:
                 # the f64 sum of the kernel's partial dW blocks leaves the dX chain: forked onto the weight-gradient lane
                 # (each layer has a workspace of its own, so the next layer's kernel cannot overwrite blocks still to be summed)
@@ -1206,62 +1297,52 @@ def plan_encoder_backward(enc, slot, g_fc2, action=None, want_dw=True, want_dact
                 plan.call("gad_gemm_dw_reduce", a, aw, side=lane)
             return
         plan.call_struct("gad_gemm_dx", a)
-        plan.tag_last("dx.%s.l%d" % (rows_kw.get("name", "fc"), rows_kw.get("layer", 0)))
+        plan.tag_last("dx.%s.l%d" % (name, l + 1))
 
     dw_lanes = []
     fused_dw = []
-    has_dx_now = [True]                # (set by layer(): a layer without a dX launch cannot take the fused call)
 
-    def dw(s, l, dz, m, action):
+    def dw(s, l, dz, has_dx):
+        """has_dx: a layer without a dX launch cannot take the fused call"""
         if not want_dw:
             return
-        a = hip.GemmDwArgs()
-        a.inp = _fwd_args(Kp=m.Kp, n_out=[m.n_out], w_off=[m.w_off], **_layer_input(enc, slot, geo, s, l, action))
-        a.dz = dz
-        a.gacc = _ptr(enc.flat.gacc)
+        args = lambda **ws: dw_args(fl, [views[s].mats[l]], layer_input(enc, views[s], l), dz, dw_workspace(fl.device, **ws))
         if FUSED_SA1_BWD and s == 0 and l > 0:
             # the two SA1 layers whose dX and dW both stream the same ~1e5-row tensors: side by side on two streams they
             # slow each other down to 2x their stand-alone durations; one kernel reads the tensors once for both
             # (workspace per backward pass: the critic's and the actor's may run at the same time)
-            ws = dw_workspace(enc.flat.device, elems=256 * 128 * 64, lane=200 + dw_lane)
-            a.partial, a.partial_elems = _ptr(ws), ws.numel()
-            fused_dw.append(a)
+            fused_dw.append(args(elems=256 * 128 * 64, lane=200 + dw_lane))
             return
-        if FUSED_WIDE_BWD and s in (1, 2) and has_dx_now[0]:
-            ws = dw_workspace(enc.flat.device, elems=WIDE_SLAB_ELEMS, lane=300 + 10 * dw_lane + 3 * s + l)
-            a.partial, a.partial_elems = _ptr(ws), ws.numel()
+        if FUSED_WIDE_BWD and s in (1, 2) and has_dx:
+            a = args(elems=WIDE_SLAB_ELEMS, lane=300 + 10 * dw_lane + 3 * s + l)
             a.row_splits = DW_REDUCE_LATER
             fused_dw.append(a)
             return
         lane = dw_lane if CONCURRENT_DW else 0         # one weight-gradient lane per pass (two measured no faster: the overlapped kernels already saturate the GPU)
         dw_lanes.append(lane)
-        ws = dw_workspace(enc.flat.device, lane=lane)
-        a.partial, a.partial_elems = _ptr(ws), ws.numel()
         if lane:
             plan.fork(lane)
-        plan.call_struct("gad_gemm_dw", a, side=lane)
+        plan.call_struct("gad_gemm_dw", args(lane=lane), side=lane)
         plan.tag_last("dw.%s.l%d" % ("sa%d" % (s + 1) if s < 3 else "fc", l + 1))
 
-    def layer(s, l, m, z, count, has_dx, **src):
-        """(dz for the dW, dz for the dX) of one layer: the dX carries the arena accumulation of dgamma / dbeta when
-        there is one, else the dW does"""
+    def layer(s, l, has_dx, **src):
+        """emits layer (s, l)'s dW and returns the dZ descriptor for its dX (None without one): the dX carries the arena
+        accumulation of dgamma / dbeta when there is one, else the dW does"""
+        v = views[s]
+        count = v.count if train else INF
         # SA3, SA2 and SA1 layers 3 / 2: the coefficients are formed in the dX / dW launches' own prologues (round 4); SA1
         # layer 1 and the FC layers keep the launch (their weight-gradient kernels read P / Q / S per lane)
-        inline = INLINE_BN_BWD and s < 3 and not (s == 0 and l == 0)
-        if not inline:
-            _bn_coef(plan, enc, slot, m, count, want_dw)
-        has_dx_now[0] = bool(has_dx)
-        d_dw = bn_dz(m, z, count, not has_dx, inline=inline, **src)
-        dw(s, l, d_dw, m, action)
-        return bn_dz(m, z, count, True, inline=inline, **src) if has_dx else None
+        inline = count if (INLINE_BN_BWD and s < 3 and not (s == 0 and l == 0)) else None
+        if inline is None:
+            emit_bn_bwd_coef(plan, enc, v, l, count, accumulate=want_dw)
+        dw(s, l, bn_dz(enc, v, l, inline_count=inline, accumulate=want_dw and not has_dx, **src), has_dx)
+        return bn_dz(enc, v, l, inline_count=inline, accumulate=want_dw, **src) if has_dx else None
 
     # ---- FC head ----
     fc1, fc2 = enc.fc_mats
-    d = layer(3, 1, fc2, slot.Zfc[1], n_fc, True, G=g_fc2)
-    dx(dict(n_rows=B, layer=2), d, fc2, fc1.n_out, epilogue=0, gout=_ptr(slot.Gfc), gout_pitch=fc1.n_out,
-       **prev_stats(fc1, slot.Zfc[0]))
-    d = layer(3, 0, fc1, slot.Zfc[0], n_fc, True, G=slot.Gfc)
-    dx(dict(n_rows=B, layer=1), d, fc1, slot.F[2].shape[1], epilogue=0, gout=_ptr(slot.dF[2]), gout_pitch=slot.F[2].shape[1])
+    c3 = views[3].feat_c
+    dx(3, 1, layer(3, 1, True, G=g_fc2), fc1.n_out, epilogue=0, gout=_ptr(slot.Gfc), gout_pitch=fc1.n_out, **prev_block(views[3], 0))
+    dx(3, 0, layer(3, 0, True, G=slot.Gfc), c3, epilogue=0, gout=_ptr(slot.dF[2]), gout_pitch=c3)
     # ---- SA3 -> SA1 ----
     for s in (2, 1, 0):
         if s == 0 and early_hook is not None and want_dw:
@@ -1269,37 +1350,24 @@ def plan_encoder_backward(enc, slot, g_fc2, action=None, want_dw=True, want_dact
             # the lane wait for the main stream up to that point, the heads' dW GEMMs included); no join, the dX chain
             # on the main stream goes straight on into SA1
             early_hook(plan, dw_lanes[-1] if dw_lanes else 0)
-        r = geo.rows[s]
-        rows_kw = dict(n_rows_dev=_ptr(r["n"]), n_rows=r["cap"], name="sa%d" % (s + 1))
-        m1, m2, m3 = enc.sa_mats[s]
-        gbuf = slot.G[s]
-        o3 = enc.bn_off[m3.bn_index]
-        cnt = geo.counts[s] if train else INF
-        # dbeta / dgamma of the pooled layer; the pooled gradient is ReLU-masked in place for its consumers
-        plan.call("gad_pool_bwd_stats", slot.dF[s], slot.argmax[s], r["G"], m3.n_out, slot.Z[s][2], m3.n_out,
-                  _bn_vec(slot, enc, m3, "scale"), _bn_vec(slot, enc, m3, "shift"), _bn_vec(slot, enc, m3, "mean"),
-                  _bn_vec(slot, enc, m3, "istd"), _ptr(slot.bstats, o3, 8), _ptr(slot.bstats, tot + o3, 8), 2 * tot, 1,
-                  slot.zmax[s])
-        d = layer(s, 2, m3, slot.Z[s][2], cnt, True, pooled=(slot.argmax[s], slot.dF[s], r["grp"]), row_w=_ptr(r["w"]))
-        dx(dict(rows_kw, layer=3), d, m3, m2.n_out, epilogue=0, gout=_ptr(gbuf[0]), gout_pitch=m2.n_out,
-           **prev_stats(m2, slot.Z[s][1]))
-        d = layer(s, 1, m2, slot.Z[s][1], cnt, True, G=gbuf[0], row_w=_ptr(r["w"]))
-        dx(dict(rows_kw, layer=2), d, m2, m1.n_out, epilogue=0, gout=_ptr(gbuf[1]), gout_pitch=m1.n_out,
-           **prev_stats(m1, slot.Z[s][0]))
+        v = views[s]
+        r = v.rows
+        m1, m2, m3 = v.mats
+        emit_pool_bwd_stats(plan, v)
+        dx(s, 2, layer(s, 2, True, pooled=True), m2.n_out, epilogue=0, gout=_ptr(v.G[0]), gout_pitch=m2.n_out, **prev_block(v, 1))
+        dx(s, 1, layer(s, 1, True, G=v.G[0]), m1.n_out, epilogue=0, gout=_ptr(v.G[1]), gout_pitch=m1.n_out, **prev_block(v, 0))
         has_dx = s > 0 or (want_daction and action is not None)
-        d = layer(s, 0, m1, slot.Z[s][0], cnt, has_dx, G=gbuf[1], row_w=_ptr(r["w"]))
+        d = layer(s, 0, has_dx, G=v.G[1])
+        # (groups per sample: the deterministic mode's scatter walks each sample's rows; the default kernels do not read it here)
+        scatter = dict(epilogue=1, feat_c=v.feat_c, row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]), grp_per_sample=v.grp_per_sample)
         if s > 0:
-            fc = slot.F[s - 1].shape[1]
             if zero_scatter:
                 plan.zero(slot.dF[s - 1])
-            # (groups per sample: the deterministic mode's scatter walks each sample's rows; the default kernels do not read it here)
-            dx(dict(rows_kw, layer=1), d, m1, fc, epilogue=1, dfeat=_ptr(slot.dF[s - 1]), feat_c=fc, row_pt=_ptr(r["pt"]),
-               row_grp=_ptr(r["grp"]), act_c=0, grp_per_sample=geo.M2 if s == 1 else 1)
+            dx(s, 0, d, v.feat_c, dfeat=_ptr(slot.dF[s - 1]), act_c=0, **scatter)
         elif has_dx:
             if zero_scatter:
                 plan.zero(slot.daction)
-            dx(dict(rows_kw, layer=1), d, m1, m1.k_in, epilogue=1, dfeat=None, feat_c=4, row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]),
-               daction=_ptr(slot.daction), act_c=6, grp_per_sample=geo.M1)
+            dx(s, 0, d, m1.k_in, dfeat=None, daction=_ptr(slot.daction), act_c=6, **scatter)
     for lane in sorted(set(dw_lanes) - {0}):
         plan.join(lane)
     return plan

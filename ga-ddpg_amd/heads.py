@@ -4,8 +4,7 @@ their input, so layer 1 is ONE GEMM over the concatenated (768 x 520) weight and
 grouped GEMMs (blockIdx.z = trunk); the policy's mean and aux heads are one (13 x 264) GEMM."""
 import torch
 
-from . import hip
-from .engine import FlatNet, MatSpec, Plan, _bn_vec, _dz, _fwd_args, _ptr, dw_workspace
+from .engine import FlatNet, MatSpec, Plan, _bn_vec, _dz, _fwd_args, _ptr, dw_args, dw_workspace, dx_args, prev_block, stage_view
 
 
 class CriticNet(object):
@@ -97,76 +96,53 @@ def plan_critic_forward(cr, hs, enc, eslot, time):
     return plan
 
 
+def _dw(plan, fl, dw_lane, mats, inp, dz, dz_off=()):
+    """a head's weight-gradient GEMM, forked onto side stream dw_lane (it feeds nothing but the optimiser: off the dX chain, like
+    the encoder's; the workspace is never shared with a forked encoder dW of lanes 1, 2)"""
+    lane = dw_lane if CONCURRENT_DW_HEADS() else 0
+    if lane:
+        plan.fork(lane)
+    plan.call_struct("gad_gemm_dw", dw_args(fl, mats, inp, dz, dw_workspace(fl.device, lane=100 + dw_lane), dz_off), side=lane)
+
+
+def _dx(plan, fl, B, dz, groups, k_valid, gout, **epi):
+    """a head's dX GEMM over groups = [(matrix, dz_off, gout_off)] into gout"""
+    plan.call_struct("gad_gemm_dx", dx_args(fl, dz, groups[0][0], k_valid, B, groups=groups, epilogue=0, gout=_ptr(gout),
+                                            gout_pitch=gout.shape[1], **epi))
+
+
+def _fc2_prev(enc, eslot):
+    """prev_* block of a head's last dX: g_feat carries the encoder's last ReLU mask (engine.plan_encoder_backward: premasked) and
+    fc[1]'s BatchNorm-backward sums land in eslot.bstats"""
+    fc2 = enc.fc_mats[1]
+    return prev_block(stage_view(eslot, [fc2], [enc.bn_off[fc2.bn_index]], Z=[eslot.Zfc[1]]), 0)
+
+
 def plan_critic_backward(cr, hs, enc, eslot, time, want_dw=True, dw_lane=1, join_dw=False):
     """consumes hs.g_out (B,9); leaves dLoss/dfeature in hs.g_feat (B,512) and the BN-backward sums
     of the encoder's last BatchNorm in eslot.bstats (which the caller must have zeroed).
-    dw_lane: the side stream the head's weight-gradient GEMMs are forked onto (they feed nothing but the optimiser: off the
-    dX chain, like the encoder's) = the lane of the encoder backward that follows (critic 1, actor 2 -- the two backward
-    passes may run concurrently); that plan's final join covers them.  join_dw: join here instead (a caller that reads the
-    gradient arena right after the head)."""
+    dw_lane: the side stream the head's weight-gradient GEMMs are forked onto = the lane of the encoder backward that follows
+    (critic 1, actor 2 -- the two backward passes may run concurrently); that plan's final join covers them.  join_dw: join here
+    instead (a caller that reads the gradient arena right after the head)."""
     plan = Plan()
     B, H, ng = hs.B, cr.hidden, cr.ng
     fl = cr.flat
     offs = [i * H for i in range(ng)]
-    tot = eslot.tot
 
-    def dw(dz, dz_off, mats, inp):
-        if not want_dw:
-            return
-        a = hip.GemmDwArgs()
-        a.inp = _fwd_args(Kp=mats[0].Kp, n_groups=len(mats), w_off=[m.w_off for m in mats],
-                          n_out=[m.n_out for m in mats], **inp)
-        a.dz = dz
-        for i, o in enumerate(dz_off):
-            a.dz_off[i] = o
-        a.gacc = _ptr(fl.gacc)
-        ws = dw_workspace(fl.device, lane=100 + dw_lane)     # never shared with a forked encoder dW (lanes 1, 2)
-        a.partial, a.partial_elems = _ptr(ws), ws.numel()
-        lane = dw_lane if CONCURRENT_DW_HEADS() else 0
-        if lane:
-            plan.fork(lane)
-        plan.call_struct("gad_gemm_dw", a, side=lane)
-
-    def dx(dz, dz_off, mats, k_valid, gout, gout_off, **epi):
-        a = hip.GemmDxArgs()
-        a.n_rows = B
-        a.dz = dz
-        a.n_groups = len(mats)
-        for i, m in enumerate(mats):
-            a.dz_off[i] = dz_off[i]
-            a.w_off[i] = m.w_off
-            a.n_out[i] = m.n_out
-            a.gout_off[i] = gout_off[i]
-        a.W = _ptr(fl.packed)
-        a.Kp = mats[0].Kp
-        a.k_valid = k_valid
-        a.epilogue = 0
-        a.gout = _ptr(gout)
-        a.gout_pitch = gout.shape[1]
-        a.grp_per_sample = 1
-        for k, v in epi.items():
-            setattr(a, k, v)
-        plan.call_struct("gad_gemm_dx", a)
+    def layer(dz, dz_off, mats, inp, k_valid, gout, gout_off, **epi):
+        if want_dw:
+            _dw(plan, fl, dw_lane, mats, inp, dz, dz_off)
+        _dx(plan, fl, B, dz, list(zip(mats, dz_off, gout_off)), k_valid, gout, **epi)
 
     # layer 3 (no activation after it)
     d3 = _dz(z=None, z_pitch=0, relu=0, gmode=0, G=_ptr(hs.g_out), g_pitch=cr.n_outputs, c=cr.n_outputs)
-    dw(d3, cr.out_off, cr.l3, _hidden_input(B, hs.Z2, cr.width, H, offs))
-    dx(d3, cr.out_off, cr.l3, H, hs.G2, offs)
+    layer(d3, cr.out_off, cr.l3, _hidden_input(B, hs.Z2, cr.width, H, offs), H, hs.G2, offs)
     # layer 2
     d2 = _dz(z=_ptr(hs.Z2), z_pitch=cr.width, relu=1, gmode=0, G=_ptr(hs.G2), g_pitch=cr.width, c=cr.width)
-    dw(d2, offs, cr.l2, _hidden_input(B, hs.Z1, cr.width, H, offs))
-    dx(d2, offs, cr.l2, H, hs.G1, offs)
+    layer(d2, offs, cr.l2, _hidden_input(B, hs.Z1, cr.width, H, offs), H, hs.G1, offs)
     # layer 1 (concatenated): one group of width 768
     d1 = _dz(z=_ptr(hs.Z1), z_pitch=cr.width, relu=1, gmode=0, G=_ptr(hs.G1), g_pitch=cr.width, c=cr.width)
-    cat = _Cat(cr.l1)
-    dw(d1, [0], [cat], _feat_input(enc, eslot, time))
-    fc2 = enc.fc_mats[1]
-    o = enc.bn_off[fc2.bn_index]
-    dx(d1, [0], [cat], fc2.n_out, hs.g_feat, [0], zprev=_ptr(eslot.Zfc[1]), zprev_pitch=fc2.n_out,
-       prev_scale=_bn_vec(eslot, enc, fc2, "scale"), prev_shift=_bn_vec(eslot, enc, fc2, "shift"),
-       prev_mean=_bn_vec(eslot, enc, fc2, "mean"), prev_istd=_bn_vec(eslot, enc, fc2, "istd"),
-       prev_dbeta=_ptr(eslot.bstats, o, 8), prev_dgamma=_ptr(eslot.bstats, tot + o, 8), stat_stride=2 * tot,
-       store_masked=1)          # g_feat carries the encoder's last ReLU mask (engine.plan_encoder_backward: premasked)
+    layer(d1, [0], [_Cat(cr.l1)], _feat_input(enc, eslot, time), enc.fc_mats[1].n_out, hs.g_feat, [0], **_fc2_prev(enc, eslot))
     if join_dw and want_dw and CONCURRENT_DW_HEADS():
         plan.join(dw_lane)
     return plan
@@ -206,57 +182,21 @@ def plan_policy_forward(po, hs, enc, eslot, time, with_log_std=False):
 
 
 def plan_policy_backward(po, hs, enc, eslot, time, dw_lane=2):
-    """consumes hs.g_out (B,13); leaves dLoss/dfeature in hs.g_feat and fc[1]'s BN sums in eslot.bstats."""
+    """consumes hs.g_out (B,13); leaves dLoss/dfeature in hs.g_feat and fc[1]'s BN sums in eslot.bstats.  The weight gradients ride
+    lane dw_lane: the encoder backward's final join covers them."""
     plan = Plan()
     B, H = hs.B, po.hidden
     fl = po.flat
-    tot = eslot.tot
     cat = _Cat([po.mean, po.extra])
-    nh = cat.n_out
 
-    def dw(dz, m, inp):
-        a = hip.GemmDwArgs()
-        a.inp = _fwd_args(Kp=m.Kp, n_out=[m.n_out], w_off=[m.w_off], **inp)
-        a.dz = dz
-        a.gacc = _ptr(fl.gacc)
-        ws = dw_workspace(fl.device, lane=100 + dw_lane)
-        a.partial, a.partial_elems = _ptr(ws), ws.numel()
-        lane = dw_lane if CONCURRENT_DW_HEADS() else 0
-        if lane:
-            plan.fork(lane)                       # weight gradients off the dX chain (the encoder backward's final join covers them)
-        plan.call_struct("gad_gemm_dw", a, side=lane)
+    def layer(dz, m, inp, k_valid, gout, **epi):
+        _dw(plan, fl, dw_lane, [m], inp, dz)
+        _dx(plan, fl, B, dz, [(m, 0, 0)], k_valid, gout, **epi)
 
-    def dx(dz, m, k_valid, gout, **epi):
-        a = hip.GemmDxArgs()
-        a.n_rows = B
-        a.dz = dz
-        a.n_groups = 1
-        a.w_off[0] = m.w_off
-        a.n_out[0] = m.n_out
-        a.W = _ptr(fl.packed)
-        a.Kp = m.Kp
-        a.k_valid = k_valid
-        a.epilogue = 0
-        a.gout = _ptr(gout)
-        a.gout_pitch = gout.shape[1]
-        a.grp_per_sample = 1
-        for k, v in epi.items():
-            setattr(a, k, v)
-        plan.call_struct("gad_gemm_dx", a)
-
-    d3 = _dz(z=None, z_pitch=0, relu=0, gmode=0, G=_ptr(hs.g_out), g_pitch=hs.g_out.shape[1], c=nh)
-    dw(d3, cat, _hidden_input(B, hs.Z2, H, H, [0]))
-    dx(d3, cat, H, hs.G2)
+    d3 = _dz(z=None, z_pitch=0, relu=0, gmode=0, G=_ptr(hs.g_out), g_pitch=hs.g_out.shape[1], c=cat.n_out)
+    layer(d3, cat, _hidden_input(B, hs.Z2, H, H, [0]), H, hs.G2)
     d2 = _dz(z=_ptr(hs.Z2), z_pitch=H, relu=1, gmode=0, G=_ptr(hs.G2), g_pitch=H, c=H)
-    dw(d2, po.l2, _hidden_input(B, hs.Z1, H, H, [0]))
-    dx(d2, po.l2, H, hs.G1)
+    layer(d2, po.l2, _hidden_input(B, hs.Z1, H, H, [0]), H, hs.G1)
     d1 = _dz(z=_ptr(hs.Z1), z_pitch=H, relu=1, gmode=0, G=_ptr(hs.G1), g_pitch=H, c=H)
-    dw(d1, po.l1, _feat_input(enc, eslot, time))
-    fc2 = enc.fc_mats[1]
-    o = enc.bn_off[fc2.bn_index]
-    dx(d1, po.l1, fc2.n_out, hs.g_feat, zprev=_ptr(eslot.Zfc[1]), zprev_pitch=fc2.n_out,
-       prev_scale=_bn_vec(eslot, enc, fc2, "scale"), prev_shift=_bn_vec(eslot, enc, fc2, "shift"),
-       prev_mean=_bn_vec(eslot, enc, fc2, "mean"), prev_istd=_bn_vec(eslot, enc, fc2, "istd"),
-       prev_dbeta=_ptr(eslot.bstats, o, 8), prev_dgamma=_ptr(eslot.bstats, tot + o, 8), stat_stride=2 * tot,
-       store_masked=1)          # g_feat carries the encoder's last ReLU mask (engine.plan_encoder_backward: premasked)
+    layer(d1, po.l1, _feat_input(enc, eslot, time), enc.fc_mats[1].n_out, hs.g_feat, **_fc2_prev(enc, eslot))
     return plan

@@ -1,6 +1,8 @@
 """Stand-alone evaluation of one `PointnetSAModule` through the fused libgaddpg path
 (pointnet2_ops.pointnet2_modules.PointnetSAModule.forward): FPS -> ball query -> de-duplicated rows
 -> gather + 3 x (1x1 conv, BatchNorm, ReLU) as FP32-MFMA GEMMs -> segment max-pool.
+Every layer launch is spelled by the emitters of engine.py over this run's stage view (engine.stage_view): the same descriptions
+the update step's encoder uses; this file decides which launches a module makes and owns their buffers.
 Cloud size: shapes the one-workgroup kernels hold keep their calls (gad_furthest_point_sampling, gad_ball_query); every other
 shape takes gad_fps_tiled (npoint + 1 launches) and, where pointnet2_utils.ball_query_uses_grid holds, gad_ball_query_grid -- the
 routing predicates of pointnet2_utils, evaluated when the _StageRun is built; its workspaces belong to it.
@@ -21,15 +23,18 @@ here) and the library's deterministic mode (the scatter is float atomics; there 
 Upstream semantics mirrored: _PointnetSAModuleBase.forward: returns
 (new_xyz (B,npoint,3) | None, new_features (B, mlp[-1], npoint | 1)).
 """
+import ctypes as C
+
 import torch
 
 from . import engine, hip
-from .engine import BN_EPS, BN_MOMENTUM, FlatNet, MatSpec, Plan, _dz, _fwd_args, _ptr
+from .engine import FlatNet, MatSpec, Plan, _ptr
 from .pointnet2_ops import pointnet2_utils as pu
 
 
 class _StageNet(object):
-    """packed parameters of one SA module (same attribute names as engine.EncoderNet)"""
+    """packed parameters of one SA module: what the emitters of engine.py read of an engine.EncoderNet (flat, running statistics,
+    bn_off), over the module's three layers"""
 
     def __init__(self, mod, device):
         seq = mod.mlps[0]
@@ -43,25 +48,9 @@ class _StageNet(object):
         for i, m in enumerate(self.mats):
             m.bn_index = i
         self.flat = FlatNet(list(mod.named_parameters()), self.mats, device)
-        # split-bf16 weight mirrors (library option "mfma_split"): layers 2 / 3, and layer 1 when its feature block is whole K-tiles
-        self.flat.enable_split([(m, (m.gather_feat_c if l == 0 else m.Kp)) for l, m in enumerate(self.mats)
-                                if (l > 0 or m.gather_feat_c >= 32)])
-        tot = sum(m.n_out for m in self.mats)
-        self.running_mean = torch.zeros(tot, dtype=torch.float32, device=device)
-        self.running_var = torch.ones(tot, dtype=torch.float32, device=device)
-        self.batches_tracked = torch.zeros(3, dtype=torch.int64, device=device)
-        self.bn_off, o = [], 0
-        for i, m in enumerate(self.mats):
-            self.bn_off.append(o)
-            with torch.no_grad():
-                self.running_mean[o:o + m.n_out].copy_(m.bn.running_mean.to(device))
-                self.running_var[o:o + m.n_out].copy_(m.bn.running_var.to(device))
-            m.bn.running_mean = self.running_mean[o:o + m.n_out]
-            m.bn.running_var = self.running_var[o:o + m.n_out]
-            self.batches_tracked[i] = int(m.bn.num_batches_tracked)
-            m.bn.num_batches_tracked = self.batches_tracked[i]
-            o += m.n_out
-        self.bn_total = tot
+        self.flat.enable_split(engine.split_mirror_layers(self.mats))          # (library option "mfma_split")
+        (self.running_mean, self.running_var, self.batches_tracked, self.bn_off,
+         self.bn_total) = engine.adopt_running_stats(self.mats, device)
         self.free = {}                                        # (B, N) -> activation sets returned by finished backwards
 
 
@@ -75,7 +64,7 @@ class _StageRun(object):
         self.group_all = mod.npoint is None
         M = 1 if self.group_all else mod.npoint
         S = N if self.group_all else mod.nsample
-        self.M, self.S = M, S
+        self.M, self.S, self.radius = M, S, None if self.group_all else float(mod.radius)
         G = B * M
         cap = G * S
         # the row lists and layer kernels hold point and row numbers, and element offsets built from them, in int32: point rows of
@@ -91,10 +80,8 @@ class _StageRun(object):
         self.fps = torch.empty(B, M, **i32)
         self.idx = torch.empty(B, M, S, **i32) if not self.group_all else None
         self.cnt = torch.empty(B, M, **i32) if not self.group_all else None
-        self.rows = dict(G=G, cap=cap, off=torch.zeros(G + 1, **i32), pt=torch.zeros(cap, **i32),
-                         grp=torch.zeros(cap, **i32), w=torch.zeros(cap, **f32), n=torch.zeros(1, **i32))
+        self.rows = r = engine.stage_rows(G, cap, device)
         if self.group_all:
-            r = self.rows
             hip.call("gad_rows_group_all", B, N, r["off"], r["pt"], r["grp"], r["w"], r["n"])
         self.Z = [torch.empty(cap, m.n_out, **f32) for m in net.mats]
         c_out = net.mats[2].n_out
@@ -115,8 +102,7 @@ class _StageRun(object):
         # raw value of every arg-max row (the backward's BatchNorm sums read it instead of gathering z[argmax])
         self.zmax = torch.empty(G, c_out, **f32) if (self.fused_pool and with_backward) else None
         self.workspaces = {}                                  # entry point -> device workspace (shapes beyond the LDS kernels)
-        self.plans = {t: self._plan(net, mod, t) for t in (True, False)}
-        self.bwd = None
+        self.G = self.dF = self.bwd = None
         if with_backward:
             self.bstats = torch.zeros(hip.STAT_REPLICAS * 2 * tot, dtype=torch.float64, device=device)
             self.coef = torch.empty(3 * tot, **f32)
@@ -124,6 +110,13 @@ class _StageRun(object):
             self.dF = torch.zeros(G, c_out, **f32)
             self.dfeat = torch.zeros(B * N, net.c_pad, **f32)
             self.grad = torch.zeros(net.flat.n, **f32)        # this call's parameter gradients (master layout)
+        # what engine's emitters read of this run: one stage whose first layer gathers [features, xyz - centroid]
+        self.view = engine.stage_view(self, net.mats, net.bn_off, rows=r, Z=self.Z, F=self.F, argmax=self.argmax, key=self.key,
+                                      zmax=self.zmax, count=self.count, G=self.G, dF=self.dF, src_xyz=self.xyz,
+                                      ctr_xyz=None if self.group_all else self.new_xyz, feat=self.feat, feat_c=net.c_pad,
+                                      action=None, act_c=0, grp_per_sample=M)
+        self.plans = {t: self._plan(net, t) for t in (True, False)}
+        if with_backward:
             self.bwd = self._plan_backward(net)
         self.bwd_xyz = None                                   # the backward plan with the coordinate gradient (coord_backward)
 
@@ -133,23 +126,9 @@ class _StageRun(object):
             ws = self.workspaces[name] = hip.workspace(name, self.xyz.device, *shape)
         return ws
 
-    def _input(self, net, mod, l):
-        """gad_gemm_fwd_args fields describing the input of layer l"""
-        r = self.rows
-        kw = dict(n_rows_dev=_ptr(r["n"]), n_rows=r["cap"], row_w=_ptr(r["w"]))
-        if l == 0:
-            kw.update(mode=1, c_in=net.c_pad + 3, src_xyz=_ptr(self.xyz),
-                      ctr_xyz=None if self.group_all else _ptr(self.new_xyz), feat=_ptr(self.feat), feat_c=net.c_pad,
-                      action=None, act_c=0, grp_per_sample=self.M, row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]))
-        else:
-            pm, po = net.mats[l - 1], net.bn_off[l - 1]
-            kw.update(mode=0, zin=_ptr(self.Z[l - 1]), zin_pitch=pm.n_out, c_in=pm.n_out, scale=_ptr(self.scale, po),
-                      shift=_ptr(self.shift, po), relu=1)
-        return kw
-
-    def _plan(self, net, mod, train):
+    def _plan(self, net, train):
         plan = Plan()
-        B, N, M, S, r, tot = self.B, self.N, self.M, self.S, self.rows, self.tot
+        B, N, M, S, r, v = self.B, self.N, self.M, self.S, self.rows, self.view
         if not self.group_all:
             # shapes beyond the LDS kernels take the entry points of the facade (pointnet2_utils: same predicates, same indices);
             # their workspaces belong to this run -- its forward is one stream, so one per entry point serves both plans
@@ -158,41 +137,22 @@ class _StageRun(object):
             else:
                 plan.call("gad_fps_tiled", self.xyz, B, N, M, 0, self.fps, self.new_xyz, self._workspace("gad_fps_tiled", B, N, M, 0))
             if pu.ball_query_uses_grid(N):
-                plan.call("gad_ball_query_grid", self.new_xyz, self.xyz, B, N, M, float(mod.radius), S, self.idx, self.cnt,
+                plan.call("gad_ball_query_grid", self.new_xyz, self.xyz, B, N, M, self.radius, S, self.idx, self.cnt,
                           self._workspace("gad_ball_query_grid", B, N, M, S))
             else:
-                plan.call("gad_ball_query", self.new_xyz, self.xyz, B, N, M, float(mod.radius), S, self.idx, self.cnt)
+                plan.call("gad_ball_query", self.new_xyz, self.xyz, B, N, M, self.radius, S, self.idx, self.cnt)
             plan.call("gad_rows_from_ball_query", self.idx, self.cnt, B * M, M, N, S, r["off"], r["pt"], r["grp"],
                       r["w"], r["n"])
         plan.zero(self.stats)
-        import ctypes as C
-        for l, m in enumerate(net.mats):
-            o = net.bn_off[l]
-            kw = self._input(net, mod, l)
-            kw.update(net.flat.split_fwd_kw(m))
+        for l in range(3):
             pooled = l == 2 and self.fused_pool
-            if pooled:
-                kw.update(pool_key=_ptr(self.key, 0, 8), pool_row_grp=_ptr(r["grp"]), pool_gamma=net.flat.p_gamma(m))
-            a = _fwd_args(W=net.flat.p_w(m), Kp=m.Kp, n_out=[m.n_out], zout=_ptr(self.Z[l]), zout_pitch=m.n_out,
-                          stat_sum=_ptr(self.stats, o, 8) if train else None,
-                          stat_sq=_ptr(self.stats, tot + o, 8) if train else None, stat_stride=2 * tot, **kw)
-            plan.call_struct("gad_gemm_fwd", a)
+            plan.call_struct("gad_gemm_fwd", engine.fwd_gemm_args(net, v, l, self.Z[l], stats=train, pooled=pooled))
             if not train:
-                plan.call("gad_bn_eval_affine", net.flat.p_gamma(m), net.flat.p_beta(m), _ptr(net.running_mean, o),
-                          _ptr(net.running_var, o), m.n_out, BN_EPS, _ptr(self.scale, o), _ptr(self.shift, o))
+                engine.emit_bn_eval_affine(plan, net, v, l)
             if pooled:
-                # finalises the layer's train-mode BatchNorm (same arithmetic and outputs as gad_bn_finalize) or takes the eval-mode
-                # scale / shift as given, then turns the keys into pooled features and arg-max rows
-                stats = (_ptr(self.stats, o, 8), _ptr(self.stats, tot + o, 8), 2 * tot, hip.Dbl(self.count)) if train else (None, None, 0, hip.Dbl(1.0))
-                run = (_ptr(net.running_mean, o), _ptr(net.running_var, o)) if train else (None, None)
-                plan.call("gad_pool_finalize", _ptr(self.key, 0, 8), m.n_out, r["G"], r["off"], *stats, net.flat.p_gamma(m),
-                          net.flat.p_beta(m), BN_EPS, BN_MOMENTUM, *run, _ptr(self.scale, o), _ptr(self.shift, o),
-                          _ptr(self.mean, o), _ptr(self.istd, o), self.F, self.argmax, self.zmax)
+                engine.emit_pool_finalize(plan, net, v, train)
             elif train:
-                plan.call("gad_bn_finalize", _ptr(self.stats, o, 8), _ptr(self.stats, tot + o, 8), 2 * tot,
-                          net.flat.p_gamma(m), net.flat.p_beta(m), m.n_out, hip.Dbl(self.count), BN_EPS, BN_MOMENTUM,
-                          _ptr(net.running_mean, o), _ptr(net.running_var, o), _ptr(self.scale, o), _ptr(self.shift, o),
-                          _ptr(self.mean, o), _ptr(self.istd, o))
+                engine.emit_bn_finalize(plan, net, v, l)
         if not self.fused_pool:
             m = net.mats[2]
             o = net.bn_off[2]
@@ -223,87 +183,43 @@ class _StageRun(object):
         padded) and this call's parameter gradients in self.grad.  Train-mode BatchNorm only (batch statistics).
         coord: also consumes self.g_new = dLoss/d(new_xyz) and leaves dLoss/dxyz in self.dxyz (see coord_backward)."""
         plan = Plan()
-        r, tot = self.rows, self.tot
-        fl = net.flat
+        r, v, fl = self.rows, self.view, net.flat
         plan.zero_multi([fl.gacc, self.bstats, self.dfeat] + ([self.dxyz, None if self.group_all else self.dctr] if coord else []))
         m1, m2, m3 = net.mats
-        o1, o2, o3 = net.bn_off
+        ws = engine.dw_workspace(fl.device, lane=0)
 
-        def vec(which, o):
-            return _ptr(getattr(self, which), o)
+        def dz(l, **src):
+            """layer l's dZ descriptor behind its coefficient launch (which also adds its dgamma / dbeta to the arena)"""
+            engine.emit_bn_bwd_coef(plan, net, v, l, self.count)
+            return engine.bn_dz(net, v, l, **src)
 
-        def bn_dz(m, o, z, accumulate, G=None, pooled=False):
-            d = dict(z=_ptr(z), z_pitch=m.n_out, scale=vec("scale", o), shift=vec("shift", o), relu=1, premasked=1,
-                     row_w=_ptr(r["w"]), c=m.n_out)
-            if not accumulate:            # first use of the layer's coefficients (the dW precedes the dX below)
-                plan.call("gad_bn_bwd_coef", _ptr(self.bstats, o, 8), _ptr(self.bstats, tot + o, 8), 2 * tot,
-                          vec("scale", o), vec("mean", o), vec("istd", o), m.n_out, hip.Dbl(self.count),
-                          _ptr(self.coef, o), _ptr(self.coef, tot + o), _ptr(self.coef, 2 * tot + o),
-                          _ptr(fl.gacc, m.g_off, 8), _ptr(fl.gacc, m.b_off, 8))
-            d["coefP"], d["coefQ"], d["coefS"] = _ptr(self.coef, o), _ptr(self.coef, tot + o), _ptr(self.coef, 2 * tot + o)
-            if pooled:
-                d.update(gmode=1, argmax=_ptr(self.argmax), dout=_ptr(self.dF), row_grp=_ptr(r["grp"]))
-            else:
-                d.update(gmode=0, G=_ptr(G), g_pitch=m.n_out)
-            return _dz(**d)
+        def dw_args(l, d):
+            return engine.dw_args(fl, [net.mats[l]], engine.layer_input(net, v, l), d, ws)
 
-        def dw_args(l, dz, m):
-            a = hip.GemmDwArgs()
-            a.inp = _fwd_args(Kp=m.Kp, n_out=[m.n_out], w_off=[m.w_off], **self._input(net, None, l))
-            a.dz = dz
-            a.gacc = _ptr(fl.gacc)
-            ws = engine.dw_workspace(fl.device, lane=0)
-            a.partial, a.partial_elems = _ptr(ws), ws.numel()
-            return a
+        def dx_args(l, d, k_valid, **epi):
+            return engine.dx_args(fl, d, net.mats[l], k_valid, r["cap"], _ptr(r["n"]), **epi)
 
-        def dw(l, dz, m):
-            plan.call_struct("gad_gemm_dw", dw_args(l, dz, m))
-
-        def bwd(l, dz, m, k_valid, **epi):
+        def bwd(l, d, k_valid):
             """dW and dX of layer l in one call (gad_gemm_bwd): SA1-like shapes (64 input channels, >= 32768 rows) stream dZ once
-            for both products, every other shape runs the same two launches as dw() + dx()"""
-            import ctypes as C
-            aw, a = dw_args(l, dz, m), dx_args(dz, m, k_valid, **epi)
+            for both products, every other shape runs the same two launches as gad_gemm_dw + gad_gemm_dx; the gradient travels
+            ReLU-masked to layer l - 1 (store_masked / premasked)"""
+            pm = net.mats[l - 1]
+            aw = dw_args(l, d)
+            a = dx_args(l, d, k_valid, epilogue=0, gout=_ptr(self.G[2 - l]), gout_pitch=pm.n_out, **engine.prev_block(v, l - 1))
             plan.keep.extend([a, aw])
             plan.call("gad_gemm_bwd", a, aw)
 
-        def dx(dz, m, k_valid, **epi):
-            plan.call_struct("gad_gemm_dx", dx_args(dz, m, k_valid, **epi))
-
-        def dx_args(dz, m, k_valid, **epi):
-            a = hip.GemmDxArgs()
-            a.n_rows_dev, a.n_rows = _ptr(r["n"]), r["cap"]
-            a.dz = dz
-            a.n_groups = 1
-            a.n_out[0] = m.n_out
-            a.W = fl.p_w(m)
-            a.Kp = m.Kp
-            a.k_valid = k_valid
-            a.grp_per_sample = 1
-            for k, v in dict(epi, **fl.split_t_kw(m)).items():
-                setattr(a, k, v)
-            return a
-
-        def prev_stats(pm, po, zprev):
-            return dict(zprev=_ptr(zprev), zprev_pitch=pm.n_out, prev_scale=vec("scale", po), prev_shift=vec("shift", po),
-                        prev_mean=vec("mean", po), prev_istd=vec("istd", po), prev_dbeta=_ptr(self.bstats, po, 8),
-                        prev_dgamma=_ptr(self.bstats, tot + po, 8), stat_stride=2 * tot, store_masked=1)
-
-        # gradients travel ReLU-masked between the layers (store_masked / premasked)
-        plan.call("gad_pool_bwd_stats", self.dF, self.argmax, r["G"], m3.n_out, self.Z[2], m3.n_out, vec("scale", o3),
-                  vec("shift", o3), vec("mean", o3), vec("istd", o3), _ptr(self.bstats, o3, 8),
-                  _ptr(self.bstats, tot + o3, 8), 2 * tot, 1, self.zmax)
-        bwd(2, bn_dz(m3, o3, self.Z[2], False, pooled=True), m3, m2.n_out, epilogue=0, gout=_ptr(self.G[0]), gout_pitch=m2.n_out,
-            **prev_stats(m2, o2, self.Z[1]))
-        bwd(1, bn_dz(m2, o2, self.Z[1], False, G=self.G[0]), m2, m1.n_out, epilogue=0, gout=_ptr(self.G[1]), gout_pitch=m1.n_out,
-            **prev_stats(m1, o1, self.Z[0]))
-        dw(0, bn_dz(m1, o1, self.Z[0], False, G=self.G[1]), m1)
-        dx(bn_dz(m1, o1, self.Z[0], True, G=self.G[1]), m1, net.c_pad, epilogue=1, dfeat=_ptr(self.dfeat), feat_c=net.c_pad,
-           row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]), act_c=0, grp_per_sample=self.M)
+        engine.emit_pool_bwd_stats(plan, v)
+        bwd(2, dz(2, pooled=True), m2.n_out)
+        bwd(1, dz(1, G=self.G[0]), m1.n_out)
+        d = dz(0, G=self.G[1])          # the dW precedes the dX below: both read the one coefficient launch
+        plan.call_struct("gad_gemm_dw", dw_args(0, d))
+        plan.call_struct("gad_gemm_dx", dx_args(0, d, net.c_pad, epilogue=1, dfeat=_ptr(self.dfeat), feat_c=net.c_pad,
+                                                row_pt=_ptr(r["pt"]), row_grp=_ptr(r["grp"]), act_c=0, grp_per_sample=self.M))
         if coord:
             # the three packed columns [c_pad, c_pad + 3) the scatter epilogue above skips: same dZ, same weights
             ga = self.group_all
-            plan.call("gad_sa_coord_grad", bn_dz(m1, o1, self.Z[0], True, G=self.G[1]), fl.p_w(m1), m1.Kp, m1.n_out, net.c_pad,
+            plan.call("gad_sa_coord_grad", d, fl.p_w(m1), m1.Kp, m1.n_out, net.c_pad,
                       _ptr(r["n"]), r["cap"], _ptr(r["pt"]), None if ga else _ptr(r["grp"]), None if ga else self.ctr,
                       None if ga else self.g_new, r["G"], self.B * self.N, self.dxyz, None if ga else self.dctr)
         plan.call("gad_grad_from_arena", fl.gacc, fl.m2p, fl.n, self.grad, 0)
@@ -320,7 +236,6 @@ def _stage_net(mod, dev):
 
 def _transpose(src, dst, B, R, C_, src_pitch, src_batch, dst_pitch, dst_batch):
     """dst[b][j][i] = src[b][i][j] (gad_transpose_batched): the (B, C, N) <-> point-major hand-over at the module boundary"""
-    import ctypes as C
     src = src if (src.is_contiguous() and src.dtype == torch.float32) else src.contiguous().float()
     hip.call("gad_transpose_batched", src, dst, B, R, C_, src_pitch, C.c_longlong(src_batch), dst_pitch, C.c_longlong(dst_batch))
 
