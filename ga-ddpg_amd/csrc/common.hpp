@@ -39,8 +39,8 @@ unsigned long long* gad_take_timing_slot();
 unsigned long long* gad_take_timing_slot(void* stream);
 int gad_take_grid_rows();       // rows the caller expects to be live (0: unknown) -- sizes the grid of the next tile launch
 
-// ---- deterministic mode (library option "deterministic": gemm.hip holds the option, the scratch and the ordered reduce, gemm.hip and
-// gemm_dw.hip the kernels' DET forms; include/gaddpg.h gad_set_option) ----
+// ---- deterministic mode (library option "deterministic": gemm.hip holds the option, the scratch and the ordered reduce, gemm_fwd.hip,
+// gemm_dx.hip and gemm_dw.hip the kernels' DET forms; include/gaddpg.h gad_set_option) ----
 // 1: every entry point's result is independent of the launch grid, grid-rows hints, stream interleaving and timing: per-workgroup
 // partials go to slots indexed by a grid-independent unit and are summed in slot order by gad_ordered_reduce (no float atomics
 // whose order decides the rounding).

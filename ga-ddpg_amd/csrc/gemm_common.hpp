@@ -1,7 +1,6 @@
 // What the units of the layer-GEMM family share (gemm.hip holds the overview and the map of the units): the operand producers,
 // LDS tile staging and the MFMA tile, the pool / statistics epilogues, the split-bf16 arithmetic, the diagnostic macros, and the
-// declarations of the option block and of the host functions that cross the units.  (The forward, dX and fused passes still sit
-// in gemm.hip: what only they use -- PoolEpi, DxEpi, namespace spw's wide-tile staging -- is here for the units they become.)
+// declarations of the option block and of the host functions that cross the units.
 #pragma once
 #include "common.hpp"
 #include <type_traits>
@@ -670,7 +669,7 @@ __device__ __forceinline__ void ktile(const unsigned char* stage, int arow, int 
 }
 }  // namespace spw
 
-// the skinny kernels (small-M layers: gemm_fwd_skinny_kernel and gemm_dx_skinny_kernel in gemm.hip, gemm_dw_skinny_kernel in gemm_dw.hip)
+// the skinny kernels (small-M layers: gemm_fwd_skinny_kernel, gemm_dx_skinny_kernel and gemm_dw_skinny_kernel, each in its pass's unit)
 #define SK_NW 8          // wavefronts per workgroup (K split); 16 -> 128-VGPR budget -> spills, 2x slower
 #define SK_CH 6          // 8-wide k groups per register chunk (17 x 1 = the whole K share in one round of loads: measured 2 % slower)
 #define SK_SP 36         // pitch (floats) of the wavefront-private operand stage of the skinny forward kernel
@@ -746,6 +745,14 @@ static DxEpi make_dxepi(const gad_gemm_dx_args& a) {
 // gemm.hip
 int check_input(const gad_gemm_fwd_args& a, const char* who);
 int coef_fallback(gad_dz_src& dz, void* stream);
+bool fits_i32_bytes(long long rows, int pitch_a, int pitch_b, int pitch_c, int pitch_d);
+double* det_stat_slots(int gx, int ncol, void* stream);
+int det_stat_reduce(const double* slots, int gx, int ncol, double* sum, double* sq, void* stream);
+// gemm_fwd.hip: the streaming forward route's predicate (check_input: mode 2 exists in that form only)
+bool fwd_streamable(const gad_gemm_fwd_args& a);
+// gemm.hip, with the streaming backward family: the SA1 streaming dX route's predicate and its launch, gad_gemm_dx's first route
+bool dx_streamable(const gad_gemm_dx_args& a, bool vec);
+int dx_stream_launch(const gad_gemm_dx_args* a, const DzSrc& d, const DxEpi& e, unsigned long long* ts, void* stream);
 // gemm_dw.hip: the streaming dW route's predicate (gad_gemm_bwd fuses what it and dx_streamable both cover), and dw_reduce_kernel
 // over `splits` partial blocks of nmax x Kp floats per group, summed into gacc
 bool dw_streamable(const gad_gemm_dw_args& a, int k_used);

@@ -1,4 +1,4 @@
-"""Plain references for the layer GEMMs of ga-ddpg_amd/csrc/gemm.hip and gemm_dw.hip (gad_gemm_fwd / gad_gemm_dx / gad_gemm_dw), written from
+"""Plain references for the layer GEMMs of ga-ddpg_amd/csrc/gemm_fwd.hip, gemm_dx.hip and gemm_dw.hip (gad_gemm_fwd / gad_gemm_dx / gad_gemm_dw), written from
 include/gaddpg.h.  torch only, no GPU needed: every function runs on CPU tensors as well as on device tensors, and in the dtype of
 its inputs -- float32 inputs give the OPERANDS exactly as the kernels form them (one rounding per fused multiply-add, float32
 subtraction of the gathered coordinates), products and sums are float64 throughout; float64 inputs give the operation itself, which
