@@ -750,7 +750,7 @@ double* det_stat_slots(int gx, int ncol, void* stream);
 int det_stat_reduce(const double* slots, int gx, int ncol, double* sum, double* sq, void* stream);
 // gemm_fwd.hip: the streaming forward route's predicate (check_input: mode 2 exists in that form only)
 bool fwd_streamable(const gad_gemm_fwd_args& a);
-// gemm.hip, with the streaming backward family: the SA1 streaming dX route's predicate and its launch, gad_gemm_dx's first route
+// gemm_bwd.hip, with the streaming backward family: the SA1 streaming dX route's predicate and its launch, gad_gemm_dx's first route
 bool dx_streamable(const gad_gemm_dx_args& a, bool vec);
 int dx_stream_launch(const gad_gemm_dx_args* a, const DzSrc& d, const DxEpi& e, unsigned long long* ts, void* stream);
 // gemm_dw.hip: the streaming dW route's predicate (gad_gemm_bwd fuses what it and dx_streamable both cover), and dw_reduce_kernel

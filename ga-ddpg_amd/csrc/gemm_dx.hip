@@ -1,5 +1,5 @@
 // dX pass of the layer-GEMM family (overview and map of the units: gemm.hip): the tile, wide, action-streaming and skinny kernels,
-// the deterministic mode's ordered scatter, the route predicates and gad_gemm_dx.  (The SA1 streaming dX kernels: gemm.hip.)
+// the deterministic mode's ordered scatter, the route predicates and gad_gemm_dx.  (The SA1 streaming dX kernels: gemm_bwd.hip.)
 #include "gemm_common.hpp"
 
 // ------------------------------------------------------------------------------------------------
