@@ -131,8 +131,11 @@ __device__ __forceinline__ float fps_wave_fmax_asm(float v) {
                  "s_nop 1" : "+v"(v));
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
-// v_min_f32 / v_max3_f32 as they are (no canonicalising v_max x, x in front: the operands are never NaN here -- distances of
-// finite coordinates, the -1 sentinel, 1e10)
+// v_min_f32 / v_max3_f32 as they are, no canonicalising v_max x, x in front.  A distance CAN be NaN (a NaN coordinate, inf - inf;
+// gaddpg.h defines the picks for such clouds) and the instructions are still right: the NaN is the result of an arithmetic
+// instruction, hence quiet, and v_min_f32 of a quiet NaN and a number returns the number -- upstream's `d < temp ? d : temp`, which
+// keeps temp.  temp therefore never becomes NaN (it starts as the -1 sentinel or 1e10 and only ever takes a smaller non-NaN
+// distance; +inf loses against 1e10 too), so v_max3_f32 and the `tm == bd` / `bd == dmax` compares never see one.
 __device__ __forceinline__ float fps_vmin(float a, float b) {
     float r;
     asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -362,7 +365,9 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((target("packed-fp32-ops"
     }
 }
 
-static int g_opt_fps_cfg = 0;     // points per thread x wavefronts for 1024 < N <= 4096: 0 = 16 x 4, 1 = 8 x 8, 2 = 4 x 16 (A/B)
+static int g_opt_fps_cfg = 0;     // points per thread x wavefronts for 1024 < N <= 4096: 0 = 16 x 4, 1 = 8 x 8, 2 = 4 x 16 (A/B);
+                                  // 3 / 4: 16 x 1 / 8 x 2 up to 1024 points, 64 x 1 / 32 x 2 beyond (tests/test_gpu_fps_forms.py
+                                  // restates this dispatch: keep its table in step)
 static int fps_tie_bits(int n) {  // log2 of upstream opt_n_threads(n) = pow2 <= min(n, 512)
     int bits = 0;
     while ((2 << bits) <= n && (2 << bits) <= 512) ++bits;

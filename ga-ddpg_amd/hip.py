@@ -274,11 +274,14 @@ def require_cuda(*tensors):
 # options this package sets when it loads the library (the library's own default of "mfma_split" is 0 = the f32 MFMA: a plain C
 # caller opts in itself); also what a test restores
 OPTION_DEFAULTS = {"mfma_split": 1, "deterministic": 0, "tnn_grid": 1}
+# library defaults other than 1 of options this package leaves alone ("fps_cfg" 0 = the measured forms of csrc/geometry.hip;
+# get_option_default answered 1 for it, so a caller restoring "the default" would have left the 8 x 8 A/B form switched on)
+LIBRARY_DEFAULTS = {"fps_cfg": 0}
 
 
 def get_option_default(name):
     """the value an option has when nothing set it: the library default, or the GAD_OPT_<name> environment override"""
-    return int(os.environ.get("GAD_OPT_" + name, OPTION_DEFAULTS.get(name, 1)))
+    return int(os.environ.get("GAD_OPT_" + name, OPTION_DEFAULTS.get(name, LIBRARY_DEFAULTS.get(name, 1))))
 
 
 _options = {}

@@ -141,7 +141,14 @@ int gad_grid_rows_hint(const int32_t* rows_host, void* stream);
 
 /* furthest_point_sampling(xyz (B,N,3) f32, npoint) -> idx (B,M) i32.  Start index 0, points with
  * |p|^2 <= 1e-3 are never selected/updated, arg-max ties resolved as the upstream block reduction
- * does.  new_xyz (B,M,3) is optional (fused gather_operation of the xyz rows).    */
+ * does.  new_xyz (B,M,3) is optional (fused gather_operation of the xyz rows).
+ * Non-finite and very large coordinates are defined, for this entry point and for gad_fps_tiled alike: the picks are upstream's,
+ * where the running minimum is `d < temp ? d : temp` from 1e10f and the arg-max a strict '>'.  A NaN distance (a NaN coordinate,
+ * inf - inf) never updates temp and never wins, an infinite or > 1e10 distance leaves temp at 1e10f, and a point whose |p|^2 is
+ * NaN is not skipped: so a point with a NaN or infinite coordinate keeps temp = 1e10f in every round and is picked again and
+ * again (only a tie at 1e10f can go to another point), and a cloud of huge coordinates (every d^2 > 1e10) is sampled by the tie
+ * rule alone.
+ * M == 1 writes index 0 (and point 0's row) even where point 0 is skipped as a candidate.  (tests/test_gpu_fps_forms.py)      */
 int gad_furthest_point_sampling(const float* xyz, int B, int N, int M, int32_t* idx,
                                 float* new_xyz /*nullable*/, void* stream);
 /* Limits of the entry point above: one workgroup keeps its whole cloud and the M picks in LDS, so N <= 16384, M <= N and
