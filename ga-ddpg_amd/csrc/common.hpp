@@ -18,7 +18,7 @@ void gad_set_error(const char* fmt, ...);
         }                                \
     } while (0)
 
-extern const char* g_gad_last_kernel;     // geometry.hip: name of the kernel family the last GEMM entry point launched
+extern const char* g_gad_last_kernel;     // library.hip: name of the kernel family the last GEMM entry point launched
 #define GAD_CHECK_LAUNCH(name)                                                          \
     do {                                                                                \
         if ((name)[0] == 'g' && (name)[4] == '_') g_gad_last_kernel = name;             \
@@ -31,7 +31,22 @@ extern const char* g_gad_last_kernel;     // geometry.hip: name of the kernel fa
 
 static inline int gad_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// ---- what crosses the geometry units (fps.hip holds their map) ----
+// the option switches (library.hip defines the block and the name table gad_geometry_set_option walks)
+struct GeometryOptions {
+    int bq_cells = 1;     // 0: no cell-list ball query (A/B; the tiled kernel takes its shapes)
+    int bq_grid = 1;      // 0: gad_ball_query_grid runs the scan kernel (A/B; the Python routes then call gad_ball_query)
+    int tnn_grid = 1;     // 0: gad_three_nn_grid runs three_nn_kernel (A/B; the Python route then calls gad_three_nn)
+    int fps_cfg = 0;      // points per thread x wavefronts for 1024 < N <= 4096: 0 = 16 x 4, 1 = 8 x 8, 2 = 4 x 16 (A/B);
+                          // 3 / 4: 16 x 1 / 8 x 2 up to 1024 points, 64 x 1 / 32 x 2 beyond (tests/test_gpu_fps_forms.py
+                          // restates this dispatch: keep its table in step)
+};
+extern GeometryOptions g_geo_opt;
 void gad_geometry_set_option(const char* name, int value, int* found);
+// group.hip: the WEIGHTED form of the deterministic ordered scatter (group_points_grad_ordered_kernel<true>), which
+// gad_three_interpolate_grad of interpolate.hip launches; the caller checks the shape and the launch
+void group_points_grad_weighted_launch(const float* grad_out, const int32_t* idx, const float* weight, int B, int C, int N, int MS,
+                                       float* grad_points, hipStream_t st);
 // the timing slot armed by gad_timing_slot() for the NEXT launch of the calling thread (NULL if none); consumed once
 unsigned long long* gad_take_timing_slot();
 // the same, carrying the wavefront issue priority gad_stream_priority() gave `stream` in bits 0..1 of the pointer (KTimer

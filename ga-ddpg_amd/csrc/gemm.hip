@@ -189,7 +189,7 @@ extern "C" int gad_set_option(const char* name, int value) {
         return GAD_OK;
     }
     int found = 0;
-    gad_geometry_set_option(name, value, &found);                                     // geometry.hip: "bq_cells"
+    gad_geometry_set_option(name, value, &found);                                     // library.hip: "bq_cells", ..
     if (found) return GAD_OK;
     GAD_REQUIRE(false, GAD_ERR_SHAPE, "set_option: unknown option '%s'", name);
     return GAD_OK;

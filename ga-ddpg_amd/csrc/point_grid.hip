@@ -1,5 +1,5 @@
 // Plan, carve and build of the uniform point grid (point_grid.hpp; what a query relies on and the margins it keeps: with the two
-// query kernels in geometry.hip).  Six launches on the caller's stream, no host synchronisation, nothing sized by the data:
+// query kernels in ball_query.hip and interpolate.hip).  Six launches on the caller's stream, no host synchronisation, nothing sized by the data:
 //   bounds   per-workgroup min / max over the points whose three coordinates are finite; clears the slice table
 //   setup    one wavefront per cloud: the box, then a grid with <= PG_GMAX cells per axis and <= `cells` in all (the budget the
 //            host derives from N alone), by one of two edge rules.

@@ -274,7 +274,7 @@ def require_cuda(*tensors):
 # options this package sets when it loads the library (the library's own default of "mfma_split" is 0 = the f32 MFMA: a plain C
 # caller opts in itself); also what a test restores
 OPTION_DEFAULTS = {"mfma_split": 1, "deterministic": 0, "tnn_grid": 1}
-# library defaults other than 1 of options this package leaves alone ("fps_cfg" 0 = the measured forms of csrc/geometry.hip;
+# library defaults other than 1 of options this package leaves alone ("fps_cfg" 0 = the measured forms of csrc/fps.hip;
 # get_option_default answered 1 for it, so a caller restoring "the default" would have left the 8 x 8 A/B form switched on)
 LIBRARY_DEFAULTS = {"fps_cfg": 0}
 

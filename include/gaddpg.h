@@ -243,7 +243,7 @@ int gad_three_nn(const float* unknown, const float* known, int B, int n, int m, 
  * unexamined point is provably farther than the current third-best d, strictly (a point at equal d and lower index would win):
  * the bound is the distance to the nearest face of the examined block that is not a border of the grid -- combined, for a query
  * outside the box, with its distance to the box along the other axes -- less the rounding of the cell function and of d
- * (derived in csrc/geometry.hip), so the test may search one ring too many, never one too few; the search
+ * (derived in csrc/interpolate.hip), so the test may search one ring too many, never one too few; the search
  * also ends when the block covers the grid (fewer than three finite points, m < 3).  A query with a non-finite coordinate
  * returns (+inf, 0) x 3 without a search.  A query unresolved after 3 rings (far outside the box, in a large void) is redone
  * by an exhaustive walk of its cloud in the same launch: exact, only slower.

@@ -1,4 +1,4 @@
-"""Plain numpy references (no torch, no HIP) for the grouping and row-building kernels of ga-ddpg_amd/csrc/geometry.hip:
+"""Plain numpy references (no torch, no HIP) for the grouping and row-building kernels of ga-ddpg_amd/csrc/ball_query.hip and group.hip:
 gad_ball_query, gad_query_and_group, gad_group_points / gad_gather_points and their gradients (include/gaddpg.h section A),
 gad_prep_points, gad_rows_from_ball_query and gad_rows_group_all (section B), written from the semantics the header states.
 numpy float32 arrays round every operation individually, which is the kernels' contract (no FMA contraction).

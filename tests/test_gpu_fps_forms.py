@@ -1,4 +1,4 @@
-"""Every form of furthest point sampling in ga-ddpg_amd/csrc/geometry.hip -- each fps_kernel<points per lane, wavefronts>
+"""Every form of furthest point sampling in ga-ddpg_amd/csrc/fps.hip -- each fps_kernel<points per lane, wavefronts>
 instantiation gad_furthest_point_sampling can launch, library option "fps_cfg" = 1 .. 4 included, and gad_fps_tiled where stated --
 called directly and held to the C oracle (oracle/cref.fps): indices bit for bit, new_xyz bit for bit against the gathered rows.
 idx starts as -7 and new_xyz as NaN, so "equal" includes that everything was written.
@@ -272,4 +272,4 @@ def test_fps_cfg_is_back_at_its_default():
     hip = _hip()
     assert hip.get_option("fps_cfg") == hip.get_option_default("fps_cfg")
     if "GAD_OPT_fps_cfg" not in os.environ:
-        assert hip.get_option_default("fps_cfg") == 0                   # the library's own default (csrc/geometry.hip: g_opt_fps_cfg)
+        assert hip.get_option_default("fps_cfg") == 0                   # the library's own default (csrc/common.hpp: GeometryOptions::fps_cfg)

@@ -1,4 +1,4 @@
-"""The grouping and row-building kernels of ga-ddpg_amd/csrc/geometry.hip -- gad_query_and_group / gad_ball_query on every route,
+"""The grouping and row-building kernels of ga-ddpg_amd/csrc/ball_query.hip and group.hip -- gad_query_and_group / gad_ball_query on every route,
 gad_group_points / gad_gather_points and their gradients, gad_prep_points, gad_rows_from_ball_query, gad_rows_group_all -- called
 directly and compared with the plain numpy references of tests/group_reference.py (pinned on the CPU by tests/test_group_reference.py).
 
@@ -11,8 +11,8 @@ Every device buffer lives between two 64-byte guard zones filled with 0xA5 that 
 (float32) or a negative sentinel (int32), and "bit for bit" includes that none of either is left in the live region.  All inputs
 come from seeded generators.
 
-Routes.  The geometry launches record no kernel name, so each query case states the dispatch predicates of geometry.hip that place
-it (_route below restates bq_use_cells / bq_use_tiled) and the tile scan below nsample = 129 is forced with option bq_cells = 0."""
+Routes.  The geometry launches record no kernel name, so each query case states the dispatch predicates of ball_query.hip that place
+it (_route below restates bq_route) and the tile scan below nsample = 129 is forced with option bq_cells = 0."""
 import functools
 import math
 
@@ -28,7 +28,7 @@ f32 = np.float32
 GUARD = 64                      # bytes
 FILL = 0xA5
 SENT = -7654321                 # what an int32 output holds before the call
-GPG_NT = 8192                   # geometry.hip: destinations per LDS tile of the deterministic gradient kernel
+GPG_NT = 8192                   # group.hip: destinations per LDS tile of the deterministic gradient kernel
 
 
 def _hip():
@@ -108,7 +108,7 @@ def _restore(name):
 
 # ----------------------------------------------------------------------------- a. fused query-and-group, every route
 def _route(N, S, C, bq_cells):
-    """where gad_query_and_group / gad_ball_query send a shape (geometry.hip: bq_use_cells, then bq_use_tiled, else the scan; the
+    """where gad_query_and_group / gad_ball_query send a shape (ball_query.hip's bq_route: cells, then tiled, else the scan; the
     radii used here are positive and small) and which grouped write-out the cells kernel then takes (SP == 64 && C <= BQC_CPIPE)"""
     in_lds = 1024 < N <= 4096
     if bq_cells and in_lds and S <= 128:

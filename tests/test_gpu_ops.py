@@ -177,7 +177,7 @@ def _bq(new_xyz, xyz, r, S):
 @pytest.mark.parametrize("case", ["uniform", "ragged_n", "clustered", "tiny_radius", "huge_radius", "degenerate", "outside",
                                   "planar", "one_centroid"])
 def test_cell_list_ball_query_matches_oracle(case):
-    """the large-cloud radius search (1024 < N <= 4096: uniform grid in LDS + per-centroid bitmap, geometry.hip
+    """the large-cloud radius search (1024 < N <= 4096: uniform grid in LDS + per-centroid bitmap, ball_query.hip
     ball_query_cells_kernel) against the C oracle on the cases that stress the grid: ragged N, clusters that overflow
     single cells, a radius so small the grid resolution is capped, a radius larger than the cloud (every point a hit,
     truncation to the first nsample by index), zero-extent clouds, centroids outside the bounding box, M % 4 != 0."""

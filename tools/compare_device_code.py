@@ -1,5 +1,7 @@
-"""Are the layer-GEMM kernels of two csrc directories the same device code?  For a refactor that moves kernels between units.
-usage: python tools/compare_device_code.py PARENT_CSRC TREE_CSRC [--work DIR] [--jobs N]   (CPU-only host; compiles every gemm*.hip of both)
+"""Are the kernels of two csrc directories the same device code?  For a refactor that moves kernels between units.
+usage: python tools/compare_device_code.py PARENT_CSRC TREE_CSRC [--parent-units U ...] [--tree-units U ...] [--work DIR] [--jobs N]
+(CPU-only host.  U: unit names or glob patterns inside that side's csrc, e.g. --parent-units geometry.hip --tree-units fps.hip
+ball_query.hip group.hip interpolate.hip library.hip, or 'gemm*.hip' for both; the default is every *.hip of the side)
 
 Each unit is compiled once with the Makefile's FLAGS plus --offload-device-only -S -Rpass-analysis=kernel-resource-usage.  The assembly
 is cut at the kernel symbols (.amdhsa_kernel), comments and directives are dropped, basic-block labels are renumbered in order of
@@ -66,14 +68,16 @@ def resources_of(log):
     return out
 
 
-def side(csrc, work, jobs):
+def side(csrc, patterns, work, jobs):
     os.makedirs(work, exist_ok=True)
-    units = sorted(os.path.basename(p) for p in glob.glob(os.path.join(csrc, "gemm*.hip")))
+    units = sorted({os.path.basename(p) for pat in patterns for p in glob.glob(os.path.join(csrc, pat))})
+    if not units:
+        sys.exit("%s: no unit matches %s" % (csrc, " ".join(patterns)))
     code, res, where = {}, {}, {}
     with concurrent.futures.ThreadPoolExecutor(jobs) as ex:
         for unit, asm, log, secs in ex.map(lambda u: compile_unit(csrc, u, work), units):
             ks = kernels_of(asm)
-            print("  %-14s %3d kernel symbols, %6d instructions  (%.0f s)" % (unit, len(ks), sum(len(v) for v in ks.values()), secs))
+            print("  %-16s %3d kernel symbols, %6d instructions  (%.0f s)" % (unit, len(ks), sum(len(v) for v in ks.values()), secs))
             for k, v in ks.items():
                 where.setdefault(k, []).append(unit)
                 code[k] = v
@@ -85,14 +89,16 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("parent")
     ap.add_argument("tree")
+    ap.add_argument("--parent-units", nargs="+", default=["*.hip"], metavar="U", help="units of the parent to compile (names or patterns)")
+    ap.add_argument("--tree-units", nargs="+", default=["*.hip"], metavar="U", help="units of the tree to compile")
     ap.add_argument("--work", default=None, help="where the .s files go (default: a temporary directory)")
     ap.add_argument("--jobs", type=int, default=4)
     a = ap.parse_args()
     work = a.work or tempfile.mkdtemp(prefix="cmpdev_")
     sides = []
-    for tag, csrc in (("parent", a.parent), ("tree", a.tree)):
+    for tag, csrc, units in (("parent", a.parent, a.parent_units), ("tree", a.tree, a.tree_units)):
         print("%s: %s" % (tag, csrc))
-        sides.append(side(os.path.abspath(csrc), os.path.join(work, tag), a.jobs))
+        sides.append(side(os.path.abspath(csrc), units, os.path.join(work, tag), a.jobs))
     (pc, pr, pw), (tc, tr, tw) = sides
     bad = 0
     for tag, w in (("parent", pw), ("tree", tw)):

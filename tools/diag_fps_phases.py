@@ -1,4 +1,4 @@
-"""cycles per part of an FPS arg-max round (wavefront 0 of cloud 0), from the -DGAD_FPS_PHASES build of geometry.hip:
+"""cycles per part of an FPS arg-max round (wavefront 0 of cloud 0), from the -DGAD_FPS_PHASES build of fps.hip:
     GAD_LIB_PATH=tools/ubench/libgaddpg_fpsphases.so python tools/diag_fps_phases.py
 (build: see tools/README.md).  Parts: 0 read pick's coordinates + distance update, 1 per-thread arg-max scan, 2 wavefront
 float max (DPP), 3 ballot / key, 4 LDS write + barrier, 5 read the wavefronts' candidates + 64-bit max + outputs."""

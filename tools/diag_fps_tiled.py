@@ -1,6 +1,6 @@
 """Times gad_fps_tiled (one launch per pick, include/gaddpg.h section A) at B = 1, M = 1024 for clouds of 8192 .. 262144 points and
 four slice sizes, i.e. four values of `groups`.  Recorded, not gated (the correctness gates are tests/test_gpu_fps_tiled.py);
-the library's rule for groups = 0 (FPS_TILED_SLICE in csrc/geometry.hip) is taken from this table.
+the library's rule for groups = 0 (FPS_TILED_SLICE in csrc/fps.hip) is taken from this table.
 
     python tools/diag_fps_tiled.py [--out profiles/fps_tiled.txt] [--rounds 5]
 

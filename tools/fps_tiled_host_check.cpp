@@ -9,8 +9,8 @@
 //
 //   cd ga-ddpg_amd/csrc && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -I../../include -munsafe-fp-atomics \
 //       -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
-//       ../../tools/fps_tiled_host_check.cpp geometry.hip point_grid.hip observe.hip gemm.hip gemm_fwd.hip gemm_dx.hip gemm_dw.hip \
-//       gemm_bwd.hip coord_grad.hip layers.hip losses.hip optim.hip plan.hip \
+//       ../../tools/fps_tiled_host_check.cpp library.hip fps.hip ball_query.hip group.hip interpolate.hip point_grid.hip \
+//       observe.hip gemm.hip gemm_fwd.hip gemm_dx.hip gemm_dw.hip gemm_bwd.hip coord_grad.hip layers.hip losses.hip optim.hip plan.hip \
 //       -o fps_tiled_host_check
 //
 // Exit status 0 and "ok" on success; a failed expectation prints its line and exits 1.
