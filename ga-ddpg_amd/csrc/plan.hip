@@ -114,6 +114,10 @@ const std::vector<reg_entry>& registry() {
         GAD_PLAN_ENTRY(gad_gemm_bwd)
         GAD_PLAN_ENTRY(gad_gemm_dw_reduce)
         GAD_PLAN_ENTRY(gad_sa_coord_grad)
+        GAD_PLAN_ENTRY(gad_fp_rows)
+        GAD_PLAN_ENTRY(gad_fp_rows_grad)
+        GAD_PLAN_ENTRY(gad_rows_act_out)
+        GAD_PLAN_ENTRY(gad_rows_act_bwd_stats)
         GAD_PLAN_ENTRY(gad_critic_loss)
         GAD_PLAN_ENTRY(gad_policy_outputs)
         GAD_PLAN_ENTRY(gad_actor_loss)

@@ -155,7 +155,8 @@ EXPORTS = (
     "gad_backproject_depth_workspace_bytes", "gad_backproject_depth", "gad_cloud_gather_affine", "gad_point_state_pack",
     "gad_query_and_group", "gad_prep_points", "gad_rows_from_ball_query", "gad_rows_group_all",
     "gad_gemm_fwd", "gad_bn_finalize", "gad_bn_eval_affine", "gad_segment_pool", "gad_pool_finalize", "gad_affine_act", "gad_transpose_batched",
-    "gad_pool_bwd_stats", "gad_bn_bwd_coef", "gad_gemm_dx", "gad_gemm_dw", "gad_gemm_bwd", "gad_gemm_dw_reduce", "gad_sa_coord_grad", "gad_critic_loss",
+    "gad_pool_bwd_stats", "gad_bn_bwd_coef", "gad_gemm_dx", "gad_gemm_dw", "gad_gemm_bwd", "gad_gemm_dw_reduce", "gad_sa_coord_grad",
+    "gad_fp_rows", "gad_fp_rows_grad", "gad_rows_act_out", "gad_rows_act_bwd_stats", "gad_critic_loss",
     "gad_policy_outputs", "gad_policy_sample", "gad_actor_loss", "gad_actor_critic_loss", "gad_mask_counts", "gad_target_noise",
     "gad_grad_from_arena", "gad_grad_from_arena_sumsq", "gad_optim_jobs", "gad_sumsq", "gad_absmax_segments", "gad_adam_step", "gad_polyak",
     "gad_pack_params", "gad_split_weights", "gad_copy_buffers",
@@ -183,6 +184,15 @@ _SIGNATURES = {
     # (dz, W, Kp, n_out, col0, n_rows_dev, n_rows, row_pt, row_grp, ctr_pt, g_new_xyz, n_groups, n_points, dxyz, dctr, stream)
     "gad_sa_coord_grad": [C.POINTER(DzSrc), _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int,
                           _vp, _vp, _vp],
+    # section C.2 (feature propagation on the layer GEMMs)
+    # (known_pm, k_pitch, idx, weight, B, n, m, C2, rows, r_pitch, col_off, stream)
+    "gad_fp_rows": [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp],
+    # (drows, r_pitch, col_off, idx, weight, B, n, m, C2, gknown_pm, k_pitch, stream)
+    "gad_fp_rows_grad": [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp],
+    # (z, z_pitch, scale, shift, B, n, C, out, stream)
+    "gad_rows_act_out": [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp],
+    # (dout, z, z_pitch, scale, shift, mean, istd, B, n, C, G, g_pitch, dbeta, dgamma, stat_stride, stream)
+    "gad_rows_act_bwd_stats": [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp],
 }
 
 

@@ -10,7 +10,10 @@ flat buffers.
 
 PointnetFPModule (feature propagation, `mlp` = one shared MLP, keys `mlp.{0,1,3,4,...}.*`): three_nn and three_interpolate of
 libgaddpg, the shared MLP as torch modules; three_nn takes the grid search of gad_three_nn_grid for the cloud sizes of
-pointnet2_utils.three_nn_uses_grid and the exhaustive gad_three_nn otherwise -- same neighbours, so the same output."""
+pointnet2_utils.three_nn_uses_grid and the exhaustive gad_three_nn otherwise -- same neighbours, so the same output.  With the
+module's `fused` switch (opt-in) the interpolation, the concatenation and the shared MLP run on the layer-GEMM family instead
+(gaddpg.h section C.2: gad_fp_rows, gad_rows_act_out and their gradients around gad_gemm_fwd / _dx / _dw; ga_ddpg_amd.fp_function
+holds the autograd wrapper)."""
 import torch.nn as nn
 
 from . import pointnet2_utils
@@ -128,15 +131,70 @@ class PointnetFPModule(nn.Module):
     features), concatenated with the skip features and passed through the shared MLP as torch modules -- the route
     _generic_forward takes for the non-fused set-abstraction forms.  The cost in m: three_nn searches a uniform grid over `known`
     (gad_three_nn_grid) where pointnet2_utils.three_nn_uses_grid(n, m) holds and walks all m known points per query otherwise;
-    the indices, the distances and hence the output and every gradient are the same bit for bit on either route"""
+    the indices, the distances and hence the output and every gradient are the same bit for bit on either route.
 
-    def __init__(self, mlp, bn=True):
+    fused (keyword-only, default False; a plain attribute that may be set after construction, not part of state_dict -- the
+    precedent is PointnetSAModuleMSG.coordinate_grad): off, forward is the composition above, unchanged.  On, a call runs on the
+    layer-GEMM family (ga_ddpg_amd.fp_function): the interpolation is written straight into the columns of one row matrix beside
+    the skip features (gad_fp_rows; nothing is materialised channel-major between the module's input and its output), every
+    layer is a gad_gemm_fwd launch with the encoder's arithmetic (FP32-MFMA or split-bf16 products, f64 BatchNorm statistics in
+    the epilogue), the backward drives gad_gemm_dx / gad_gemm_dw, and under hip.deterministic() every tensor is bit-reproducible
+    with the library option alone.  three_nn and the three weight lines stay as they are.  The fused path takes a call where
+    bn=True, known is given, the inputs are CUDA float32, B * n >= 2, every layer width is a multiple of 4 up to 1024 (mlp[0]
+    itself may be any size up to 1024) and the row tensors stay within 32-bit element indexing; every other call -- known=None,
+    bn=False, a backward through eval-mode BatchNorm, CPU tensors -- takes the composition exactly as with the switch off.
+    `last_route` says which one the last forward took ("fused" | "composed").  state_dict keys and values, load_state_dict,
+    .train() / .eval() / .to() and ordinary torch optimizers work as before (after the first fused call the parameters and the
+    running statistics are views of flat buffers, as for the set-abstraction modules); running statistics and
+    num_batches_tracked advance as torch's do.
+    Measured (tools/bench_fp_module.py, profiles/fp_fused.txt; forward + backward, train mode, B = 16, the four decoder levels of
+    a PointNet++ SSG segmentation network on 4096-point clouds, us per call composed / fused):
+    768-256-256 at n 64: 729 / 499 (1.46 x); 384-256-256 at n 256: 737 / 502 (1.47 x); 320-256-128 at n 1024: 766 / 512
+    (1.50 x); 134-128-128-128 at n 4096: 1072 / 735 (1.46 x).  The fused path is ahead at every level; no level was found
+    where the composition wins.  The three coarse levels follow the host's launch rate on either path (the same time
+    whatever n), only the finest is long enough for device time to show"""
+
+    def __init__(self, mlp, bn=True, *, fused=False):
         super().__init__()
         self.mlp = build_shared_mlp(list(mlp), bn)
+        self.bn = bool(bn)
+        self.fused = bool(fused)
+        self.last_route = None            # "fused" | "composed": the route the last forward took
+
+    def _fused_call(self, unknown, known, unknow_feats, known_feats):
+        """does this call take the fused path (see the class docstring)"""
+        import torch
+        from .. import fp_function
+        if not (self.fused and self.bn and known is not None and known_feats is not None):
+            return False
+        ts = [unknown, known, known_feats] + ([] if unknow_feats is None else [unknow_feats])
+        if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in ts):
+            return False
+        if unknown.dim() != 3 or known.dim() != 3 or known_feats.dim() != 3 or (unknow_feats is not None and unknow_feats.dim() != 3):
+            return False
+        B, n, m = unknown.shape[0], unknown.shape[1], known.shape[1]
+        c1 = 0 if unknow_feats is None else unknow_feats.shape[1]
+        if known_feats.shape[0] != B or known_feats.shape[2] != m or (c1 and (unknow_feats.shape[0] != B or unknow_feats.shape[2] != n)):
+            return False
+        if not fp_function.fits(self, B, n, m, c1, known_feats.shape[1]):
+            return False
+        if not self.training and torch.is_grad_enabled():       # a backward through eval-mode BatchNorm: the composition has one
+            feats = [known_feats] + ([] if unknow_feats is None else [unknow_feats])
+            if any(t.requires_grad for t in feats) or any(p.requires_grad for p in self.parameters()):
+                return False
+        return True
 
     def forward(self, unknown, known, unknow_feats, known_feats):
         """unknown (B,n,3), known (B,m,3) | None, unknow_feats (B,C1,n) | None, known_feats (B,C2,m) -> (B,mlp[-1],n)"""
         import torch
+        if self._fused_call(unknown, known, unknow_feats, known_feats):
+            from ..fp_function import fp_module_forward
+            dist, idx = pointnet2_utils.three_nn(unknown, known)
+            w = 1.0 / (dist + 1e-8)
+            w = w / w.sum(dim=2, keepdim=True)
+            self.last_route = "fused"
+            return fp_module_forward(self, idx, w, unknow_feats, known_feats)
+        self.last_route = "composed"
         if known is not None:
             dist, idx = pointnet2_utils.three_nn(unknown, known)
             w = 1.0 / (dist + 1e-8)

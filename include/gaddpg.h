@@ -66,7 +66,9 @@ int gad_abi_version(void);                 /* bumped on any signature change or 
                                             * gad_backproject_depth_workspace_bytes, gad_cloud_gather_affine and
                                             * gad_point_state_pack (additive: section A.2, depth frame -> point state);
                                             * gad_sa_coord_grad (additive: section C, the coordinate columns of a
-                                            * set-abstraction stage's first-layer gradient)  */
+                                            * set-abstraction stage's first-layer gradient); gad_fp_rows, gad_fp_rows_grad,
+                                            * gad_rows_act_out and gad_rows_act_bwd_stats (additive: section C.2, the entry
+                                            * and exit of a feature-propagation module on the layer GEMMs)  */
 /* diagnostics: which kernel family the last gad_gemm_fwd / _dx / _dw / _bwd call routed to ("gemm_fwd(stream)",
  * "gemm_dx(wide)", "gemm_bwd(stream)", "gemm_dw" = generic tile kernel, ...); bench.py labels its per-kernel table
  * with it instead of restating the routing rules.                                                  */
@@ -665,6 +667,42 @@ int gad_sa_coord_grad(const gad_dz_src* dz, const float* W, int Kp, int n_out, i
                       int n_rows, const int32_t* row_pt, const int32_t* row_grp /*nullable*/,
                       const int32_t* ctr_pt /*nullable*/, const float* g_new_xyz /*nullable*/, int n_groups, int n_points,
                       float* dxyz, float* dctr /*nullable*/, void* stream);
+
+/* ---- C.2 feature propagation on the layer GEMMs (additive under ABI 12) ----
+ * A PointnetFPModule (upstream pointnet2_modules.py: three_interpolate -> torch.cat -> SharedMLP) is a stack of dense-row layers:
+ * gad_gemm_fwd / _dx / _dw with n_rows_dev = row_w = NULL run them, the first with an identity input (mode 0, scale = NULL,
+ * relu 0).  These four entry points stand where the gather and the max-pool stand for a set-abstraction stage: the row matrix
+ * at the entry and its gradient, the activation at the exit and its gradient statistics.  Each takes the caller's stream,
+ * allocates nothing, never synchronises the host; a zero-sized shape is GAD_OK without a launch.
+ *
+ * gad_fp_rows: three_interpolate written as GEMM input rows.  known_pm (B * m, k_pitch) point-major features of the known
+ *   points, idx / weight (B, n, 3) of gad_three_nn and the caller's inverse-distance weights;
+ *   rows[b * n + i][col_off + c] = (w0 * f[j0][c] + w1 * f[j1][c]) + w2 * f[j2][c] for c < C2, every product and sum rounded on its
+ *   own: gad_three_interpolate's output, transposed, bit for bit.  Columns outside [col_off, col_off + C2) are not written.
+ *   Indices are not range-checked (as for gad_three_interpolate).  16-byte accesses where C2, k_pitch, r_pitch, col_off are
+ *   multiples of 4 and both base addresses 16-byte aligned, 4-byte ones otherwise.  k_pitch >= C2 and col_off + C2 <= r_pitch
+ *   (GAD_ERR_SHAPE otherwise), m >= 1 unless there is nothing to write.
+ * gad_fp_rows_grad: its gradient, gknown_pm[b * m + j_k][c] += w_k * drows[b * n + i][col_off + c] with float atomics into a
+ *   buffer the caller cleared; an element no entry reaches stays exactly 0.  Option "deterministic": GAD_ERR_UNSUPPORTED before
+ *   any launch (nothing is written) -- the caller transposes drows and takes gad_three_interpolate_grad's ordered form.        */
+int gad_fp_rows(const float* known_pm, int k_pitch, const int32_t* idx, const float* weight, int B, int n, int m, int C2,
+                float* rows, int r_pitch, int col_off, void* stream);
+int gad_fp_rows_grad(const float* drows, int r_pitch, int col_off, const int32_t* idx, const float* weight, int B, int n, int m,
+                     int C2, float* gknown_pm, int k_pitch, void* stream);
+/* gad_rows_act_out: the module's output, out (B, C, n) channel-major = relu(fma(z, scale, shift)) of the last layer's raw
+ *   z (B * n, z_pitch): gad_affine_act's arithmetic with the transpose folded in (an LDS tile: both sides coalesced).
+ *   Any C >= 0, z_pitch >= C.
+ * gad_rows_act_bwd_stats: the top of the backward.  dout (B, C, n) channel-major; G (B * n, g_pitch) row-major = dout where
+ *   fma(z, scale, shift) > 0, else 0 (the layer's dX / dW take it as `premasked`); dbeta[c] += sum_r G[r][c],
+ *   dgamma[c] += sum_r G[r][c] * (z[r][c] - mean[c]) * istd[c], f64 sums into the GAD_STAT_REPLICAS replicas stat_stride
+ *   doubles apart (what gad_pool_bwd_stats with mask_in_place gives a pooled layer whose every row is its own group).
+ *   Any C >= 0, z_pitch and g_pitch >= C, stat_stride >= C.  Option "deterministic": per-workgroup sums stored into slots of
+ *   a grid that depends on (B, n, C) alone and added in slot order into replica 0 (two calls are bit-identical).              */
+int gad_rows_act_out(const float* z, int z_pitch, const float* scale, const float* shift, int B, int n, int C, float* out,
+                     void* stream);
+int gad_rows_act_bwd_stats(const float* dout, const float* z, int z_pitch, const float* scale, const float* shift,
+                           const float* mean, const float* istd, int B, int n, int C, float* G, int g_pitch, double* dbeta,
+                           double* dgamma, int stat_stride, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * D. heads' losses (forward value + gradient wrt head outputs in one pass)
