@@ -612,7 +612,10 @@ typedef struct {
     gad_dz_src dz;
     int32_t dz_off[GAD_MAX_GROUPS];
     double* gacc;              /* f64 gradient arena, packed layout; group g at gacc + in.w_off[g]; ADDED to */
-    int32_t row_splits;        /* rows are divided over this many blocks (0 -> auto)               */
+    int32_t row_splits;        /* rows are divided over this many blocks (0 -> auto): block s of the generic tile kernels takes
+                                * the live rows [s * chunk, (s + 1) * chunk), chunk = ceil(ceil(live / row_splits) / 32) * 32
+                                * (blocks past the live rows add nothing).  The deterministic mode's order is defined by this
+                                * rule: the arena receives the blocks' partial sums in block order (see "deterministic")        */
     float* partial;            /* caller workspace for the per-split partial tiles (NULL -> f64 atomics) */
     int64_t partial_elems;     /* capacity of `partial` in floats                                   */
 } gad_gemm_dw_args;

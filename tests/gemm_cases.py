@@ -37,6 +37,34 @@ def _default(name):
     return hip.get_option_default(name) if name in ("mfma_split", "deterministic") else OPTION_DEFAULTS[name]
 
 
+def _supplied(v, dev):
+    """a caller-supplied array (numpy or torch) as a contiguous device tensor of its own dtype"""
+    t = v if torch.is_tensor(v) else torch.from_numpy(v)
+    return t.to(dev).contiguous()
+
+
+def _supply(case, operands, dev):
+    """caller-supplied operands: every entry replaces the case's drawn tensor of that name (shape and dtype are the caller's to get
+    right: the drawn one is asserted against); `pvec`: the list of the previous layer's four vectors"""
+    for k, v in (operands or {}).items():
+        if isinstance(v, (list, tuple)):
+            new = [_supplied(x, dev) for x in v]
+            assert [tuple(x.shape) for x in new] == [tuple(x.shape) for x in getattr(case, k)], k
+        else:
+            new = _supplied(v, dev)
+            old = getattr(case, k)
+            assert old is not None and tuple(new.shape) == tuple(old.shape) and new.dtype == old.dtype, (k, new.shape, new.dtype)
+        setattr(case, k, new)
+
+
+def _prefill(t, init):
+    """what an accumulator holds before the launch: zeros, or the caller's initial values"""
+    if init is None:
+        t.zero_()
+    else:
+        t.copy_(_supplied(init, t.device).reshape(t.shape))
+
+
 def matmul32(a, b):
     """torch's float32 matmul (no TF32): the baseline that is not code under test"""
     was = torch.backends.cuda.matmul.allow_tf32
@@ -162,14 +190,18 @@ class Fwd(Case):
     it) or GATHER input (gather = dict(feat_c, act_c, gps, ctr)); groups through zin_off / out_off / n_out; live: device row count
     (rows = the static bound); pool = dict(gsz, gamma): the fused max-pool; in_stat: the input layer's BatchNorm finalised by the launch.
     split: the call carries the forward split-bf16 mirror of W (split_cases.Mirror; one group).  pre_Kp (with gather and c_in): mode 2,
-    the c_in-channel ACT input recomputed from the gathered rows and pre_W (c_in, pre_Kp), then scale / shift / ReLU."""
+    the c_in-channel ACT input recomputed from the gathered rows and pre_W (c_in, pre_Kp), then scale / shift / ReLU.
+    Hooks (tests/test_gpu_deterministic_kernels.py; the drawn operands of a case without them are unchanged): maps = dict(row_pt,
+    row_grp, npts, nsmp): the caller's row maps of a gathered input; operands = {attribute: array}: replaces drawn tensors of the
+    same shape and dtype; init = {"stats": array}: what the statistics hold before the launch in place of zeros."""
     entry = "gad_gemm_fwd"
 
     def __init__(self, rows, Kp, n_out, c_in=None, extra=False, ones=False, affine=True, relu=1, zin_off=None, out_off=None,
                  zout_pitch=None, stats=True, row_w=True, live=None, gather=None, pool=None, in_stat=False, zout=True, seed=1,
-                 w_scale=0.05, split=False, pre_Kp=None):
+                 w_scale=0.05, split=False, pre_Kp=None, maps=None, operands=None, init=None):
         dev = torch.device("cuda")
         g = _gen(seed)
+        self.init = dict(init or {})
         self.rows, self.Kp, self.n_out, self.ng = rows, Kp, list(n_out), len(n_out)
         self.r = rows if live is None else live
         self.nrows = None if live is None else torch.tensor([live], dtype=torch.int32, device=dev)
@@ -188,6 +220,8 @@ class Fwd(Case):
             self.ones_col = -1
             npts = max(self.r // 3, 64)
             ngrp = (max(self.r // 8, 8) + gps - 1) // gps * gps
+            if maps is not None:
+                npts, ngrp = maps["npts"], maps["nsmp"] * gps
             self.npts, self.ngrp, self.nsmp = npts, ngrp, ngrp // gps
             self.feat = torch.randn(npts, fc, device=dev, generator=g).abs()
             self.src = torch.rand(npts, 3, device=dev, generator=g)
@@ -195,6 +229,8 @@ class Fwd(Case):
             self.action = torch.randn(self.nsmp, ac, device=dev, generator=g) if ac else None
             self.row_pt = torch.randint(0, npts, (rows,), device=dev, generator=g, dtype=torch.int32)
             self.row_grp = torch.sort(torch.randint(0, ngrp, (rows,), device=dev, generator=g, dtype=torch.int32)).values.contiguous()
+            if maps is not None:
+                self.row_pt, self.row_grp = _supplied(maps["row_pt"], dev), _supplied(maps["row_grp"], dev)
             if pre_Kp is not None:
                 assert self.gk <= pre_Kp
                 self.pre_W = torch.randn(c_in, pre_Kp, device=dev, generator=g) * 0.3
@@ -224,6 +260,7 @@ class Fwd(Case):
             if pool.get("gamma") == "mixed":
                 self.gamma = torch.randn(self.n_out[0], device=dev, generator=g)
                 self.gamma[::5] = 0.0
+        _supply(self, operands, dev)
         if in_stat:
             import numpy as np
             from tests import layer_reference as lr
@@ -278,7 +315,7 @@ class Fwd(Case):
         if self.zout is not None:
             self.zout.fill_(nan)
         if self.stats is not None:
-            self.stats.zero_()
+            _prefill(self.stats, self.init.get("stats"))
         if self.pool is not None:
             self.key.zero_()
         if self.in_stat:
@@ -459,14 +496,17 @@ class Dx(Case):
     dz_off / gout_off / n_out; prev: the previous layer's BatchNorm-backward sums (+ store_masked); scatter = dict(feat_c, act_c, gps,
     dfeat, daction): epilogue 1.  P and the row weights are powers of two (tests/split_cases.DxWide): dZ has a single rounding.
     pad_cols: columns of gout / zprev behind the last group's that no group writes (0: pitch = k_valid, what the streaming routes
-    take); split: the call carries the transposed split-bf16 mirror of W (split_cases.Mirror; one group)."""
+    take); split: the call carries the transposed split-bf16 mirror of W (split_cases.Mirror; one group).
+    Hooks as for Fwd: maps (the scatter epilogue's row maps, point and sample counts), operands, init = {"dfeat" / "daction" /
+    "bst": array}: the accumulators' contents before the launch in place of zeros."""
     entry = "gad_gemm_dx"
 
     def __init__(self, rows, n_out, Kp, k_valid, dz_off=None, gout_off=None, g_pitch=None, z=True, relu=1, premasked=1, dscale=False,
                  coef=True, row_w=True, prev=False, store_masked=1, live=None, pooled=None, scatter=None, bn=False, seed=2, w_scale=0.05,
-                 pad_cols=4, split=False):
+                 pad_cols=4, split=False, maps=None, operands=None, init=None):
         dev = torch.device("cuda")
         g = _gen(seed)
+        self.init = dict(init or {})
         self.rows, self.Kp, self.kv, self.n_out, self.ng = rows, Kp, k_valid, list(n_out), len(n_out)
         self.r = rows if live is None else live
         self.nrows = None if live is None else torch.tensor([live], dtype=torch.int32, device=dev)
@@ -500,6 +540,9 @@ class Dx(Case):
             self.row_pt = torch.randint(0, self.npts, (rows,), device=dev, generator=g, dtype=torch.int32)
             self.row_pt[: rows // 3] = 5                                   # many rows on one point
             self.row_grp = torch.sort(torch.randint(0, ngrp, (rows,), device=dev, generator=g, dtype=torch.int32)).values.contiguous()
+            if maps is not None:
+                self.npts, self.nsmp = maps["npts"], maps["nsmp"]
+                self.row_pt, self.row_grp = _supplied(maps["row_pt"], dev), _supplied(maps["row_grp"], dev)
             self.dfeat = torch.zeros(self.npts, fc, device=dev) if scatter.get("dfeat", True) else None
             self.daction = torch.zeros(self.nsmp, ac, dtype=torch.float64, device=dev) if (ac and scatter.get("daction", True)) else None
             self.width = k_valid
@@ -522,6 +565,7 @@ class Dx(Case):
             self.bn_istd = torch.rand(C, device=dev, generator=g) + 0.5
             self.dscale = torch.pow(2.0, torch.randint(-1, 2, (C,), device=dev, generator=g).float())     # P = scale: a power of two
             self.dshift = torch.randn(C, device=dev, generator=g) * 0.3
+        _supply(self, operands, dev)
         self.mirror = None
         if split:
             from tests.split_cases import Mirror
@@ -567,13 +611,13 @@ class Dx(Case):
         """everything the launch may write, pre-filled"""
         self.bn_prepare()
         if self.scatter is not None:
-            for t in (self.dfeat, self.daction):
+            for k, t in (("dfeat", self.dfeat), ("daction", self.daction)):
                 if t is not None:
-                    t.zero_()
+                    _prefill(t, self.init.get(k))
         else:
             self.gout.fill_(float("nan"))
             if self.prev:
-                self.bst.zero_()
+                _prefill(self.bst, self.init.get("bst"))
 
     def collect(self):
         out = {}
@@ -718,10 +762,11 @@ class Dx(Case):
 # ----------------------------------------------------------------------------------------------------------------- dW
 class Dw(Case):
     """gad_gemm_dw: `inp` (a Fwd case: how the layer's input rows are produced) and `dz` (a Dx case: the gradient source) over the
-    same rows.  The arena is pre-filled (the entry point ADDS); partial: the caller's split workspace or NULL (f64 atomics)."""
+    same rows.  The arena is pre-filled (the entry point ADDS); partial: the caller's split workspace or NULL (f64 atomics);
+    init = {"gacc": array}: the caller's arena contents in place of the drawn pre-fill."""
     entry = "gad_gemm_dw"
 
-    def __init__(self, inp, dz, dz_off=None, partial=True, row_splits=0):
+    def __init__(self, inp, dz, dz_off=None, partial=True, row_splits=0, init=None):
         dev = torch.device("cuda")
         assert inp.rows == dz.rows and inp.r == dz.r
         self.inp, self.dz, self.row_splits = inp, dz, row_splits
@@ -731,6 +776,9 @@ class Dw(Case):
         g = _gen(99)
         self.prefill = (torch.randint(-16, 17, (self.total,), device=dev, generator=g).double() / 8.0)     # non-zero, few bits
         self.prefill[self.prefill == 0] = 0.125
+        if init is not None and "gacc" in init:                         # caller-supplied arena contents
+            self.prefill = _supplied(init["gacc"], dev).double().reshape(-1)
+            assert self.prefill.numel() == self.total
         self.gacc = self.prefill.clone()
         self.ws = torch.empty(8 * 1024 * 1024, device=dev) if partial else None
 
